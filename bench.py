@@ -3,7 +3,18 @@
 1/2/4/8 GPU").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload big|moderate|NAME]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N ... bench.py --gpus N ...      (N > 1, RCCL)
+
+A plain run does what the headline figure needs and no more: set up, ramp the
+clocks, W warm-up steps, the K timed steps, one JSON line (value, ms_per_step,
+hbm_gbps, config). --dump-outputs DIR then writes every matrix's y as the last
+timed step left it to DIR/<matrix>.npy (float64; the inputs are seeded, so two
+builds can be compared file by file; above 48 MB in all, a fixed seeded sample
+of each matrix's rows). --full adds, in runs of their own after the timed
+steps, everything else described below: the roofline of the dominant kernel,
+one launch per matrix, the fp32 pass, the oracle parity check (exit 3 if it
+fails), the Serena-only step (config 5) and the CPU baseline.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (a plain `python
 bench.py --gpus N`), bench.py launches the N ranks itself: N child processes
@@ -552,7 +563,34 @@ def parse_args(argv=None):
                     help="nccl (= RCCL, the product path); gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--launch-timeout", type=float, default=0.0,
                     help="launcher mode: stop every rank after this many seconds (0: no limit)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline "
+                         "figure: roofline of the dominant kernel, one launch per matrix, the fp32 pass, "
+                         "the oracle parity check, the Serena-only step (config 5) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write each matrix's y as the last timed step left it to DIR/<matrix>.npy "
+                         "(float64; a fixed seeded sample of the rows where the set exceeds the size cap)")
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 48 * 10 ** 6  # cap of everything --dump-outputs writes
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, slices, rank, world):
+    """Every slice's y (this rank's rows of the matrix, as the last timed step
+    left them) as float64 .npy files. Above the cap every matrix gets an equal
+    share of it: a matrix with more rows is written as a sample of them, drawn
+    once from a fixed seed (the same rows in every run, in row order)."""
+    os.makedirs(path, exist_ok=True)
+    cap = max(1, DUMP_BYTES // 8 // max(1, world * len(slices)))
+    for i, s in enumerate(slices):
+        y = s.y64[: s.m_local].cpu().numpy()
+        if s.m_local > cap:
+            rows = np.sort(np.random.RandomState(DUMP_SEED + i).permutation(s.m_local)[:cap])
+            y = y[rows]
+        np.save(os.path.join(path, s.name + (f".rank{rank}" if world > 1 else "") + ".npy"),
+                np.ascontiguousarray(y, dtype=np.float64))
 
 
 def main():
@@ -596,19 +634,83 @@ def main():
     t_setup = time.perf_counter()
     W = Workload(names, rank, world, handle, device, args)
     slices, batches, overlap, exchanges64 = W.slices, W.batches, W.overlap, W.exchanges64
-    step, spmv_all, stream = W.step, W.spmv_all, W.stream
     log(f"setup {time.perf_counter() - t_setup:.1f}s: {len(slices)} matrices, "
         f"{sum(s.nnz_global for s in slices) / 1e6:.1f} M stored nnz, world={world}")
 
     ramp_steps = W.ramp(args.ramp_ms, device)
     elapsed, e_start, e_end = W.timed(args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, slices, rank, world)
+    flops_step, bytes_step = W.totals()
+    value = flops_step * args.steps / elapsed / 1e9
+    hbm_gbs = bytes_step * args.steps / elapsed / 1e9
+    per_step = -(-len(slices) // 32) if batches else len(slices)  # 32 matrices per batch launch
+
+    # everything beside the headline figure: runs of their own, after the timed steps
+    extra, check_ok = (full_measurements(args, W, handle, rank, world, device, per_step, e_start, e_end)
+                       if args.full else ({}, True))
+
+    if rank == 0:
+        out = {
+            "metric": METRIC,
+            "value": round(value, 2),
+            "unit": "GFLOP/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: seeded surrogates of the SuiteSparse matrices (same m, stored nnz, "
+                    "structure family; SURVEY App. A) - no .mtx data offline",
+            "config": {
+                "workload": f"{args.workload}-set CSR SpMV fp64, {len(slices)} matrices per step"
+                            + (f", row-partitioned + RCCL {args.exchange} exchange of x" if world > 1 else ""),
+                "matrices": len(slices),
+                "nnz_stored_total": int(sum(s.nnz_global for s in slices)),
+                "parallelism": f"row-partition x{world}" if world > 1 else "1 GPU",
+                "launch": "one rsp_spmv per matrix" if args.no_batch else
+                          (f"rsp_spmv_batch ({per_step} launch(es) of <= 32 matrices per step part): "
+                           + ("interior, then boundary" if overlap else "whole step")),
+                "collective": (("halo all_to_all_single" + ("" if args.halo_unpack else ", received in place")
+                                 + ("" if args.no_bucket else
+                                 " (one per step, bucketed over the matrices)")
+                                 + (", interior tiles overlapped" if overlap else "")
+                                 if args.exchange == "halo" else "all_gather_into_tensor")
+                               + f" over {args.dist_backend}"
+                               + (" (RCCL, xGMI)" if args.dist_backend == "nccl" else " (rehearsal)"))
+                if world > 1 else None,
+                "halo_bytes_per_step_rank0": (sum(ex.bytes_per_exchange for _, ex in exchanges64)
+                                              if exchanges64 else None),
+            },
+            "setup_ramp": {"ms": args.ramp_ms, "steps": ramp_steps,
+                           "note": "untimed steps before the warm-up so the GPU clocks reach steady "
+                                   "state; the timed region is exactly `steps` full steps"},
+            "hbm_gbps": round(hbm_gbs, 1),
+            "full": bool(args.full),
+        }
+        out.update(extra)
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+    if not check_ok:
+        sys.exit(3)
+
+
+def full_measurements(args, W, handle, rank, world, device, per_step, e_start, e_end):
+    """--full: what the benchmark measures and checks beside the headline
+    figure, each in runs of its own after the timed steps. Returns (the
+    result line's further keys, whether the parity check passed)."""
+    slices, batches, overlap = W.slices, W.batches, W.overlap
+    step, spmv_all, stream = W.step, W.spmv_all, W.stream
     big = max(slices, key=lambda s: s.nnz_global)
-    y_step_t = big.y64.clone()  # checked against a whole SpMV below
+    y_step_t = big.y64.clone()  # as the last timed step left it: checked against a whole SpMV below
 
     # dominant kernel, this rank: algorithmic bytes / average launch duration.
     # N = 1: the timed region is nothing but back-to-back launches of it; N > 1:
     # the same K steps again without the exchange (kernel-only), same stream.
-    per_step = -(-len(slices) // 32) if batches else len(slices)  # 32 matrices per batch launch
     launches = args.steps * per_step
     if world == 1:
         kern_ms = e_start.elapsed_time(e_end)
@@ -656,15 +758,6 @@ def main():
     step(exchange=False, events=ev)
     torch.cuda.synchronize()
     per_matrix = {s.name: round(ev[i][0].elapsed_time(ev[i][1]) * 1e3, 2) for i, s in enumerate(slices)}
-
-    # totals over ranks
-    tot = torch.tensor([float(sum(2.0 * s.nnz_local for s in slices)), float(bytes64)],
-                       dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(tot)
-    flops_step, bytes_step = float(tot[0]), float(tot[1])
-    value = flops_step * args.steps / elapsed / 1e9
-    hbm_gbs = bytes_step * args.steps / elapsed / 1e9
 
     # fp32 companion measurement (outside the timed region), launched as the fp64 step
     b32 = (SpmvBatch(handle, [s.mat32 for s in slices], [s.x32() for s in slices],
@@ -762,47 +855,11 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args.workload, args.cpu_seconds, args.cpu_threads)
 
+    extra = {}
     if rank == 0:
         traffic, traffic_src = (pmc_traffic(args.workload, bool(batches)) if world == 1  # PMC run was N = 1
                                 else (None, {"file": None, "note": "PMC summaries are recorded at N = 1"}))
-        out = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GFLOP/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: seeded surrogates of the SuiteSparse matrices (same m, stored nnz, "
-                    "structure family; SURVEY App. A) - no .mtx data offline",
-            "config": {
-                "workload": f"{args.workload}-set CSR SpMV fp64, {len(slices)} matrices per step"
-                            + (f", row-partitioned + RCCL {args.exchange} exchange of x" if world > 1 else ""),
-                "matrices": len(slices),
-                "nnz_stored_total": int(sum(s.nnz_global for s in slices)),
-                "parallelism": f"row-partition x{world}" if world > 1 else "1 GPU",
-                "launch": "one rsp_spmv per matrix" if args.no_batch else
-                          (f"rsp_spmv_batch ({per_step} launch(es) of <= 32 matrices per step part): "
-                           + ("interior, then boundary" if overlap else "whole step")),
-                "collective": (("halo all_to_all_single" + ("" if args.halo_unpack else ", received in place")
-                                 + ("" if args.no_bucket else
-                                 " (one per step, bucketed over the matrices)")
-                                 + (", interior tiles overlapped" if overlap else "")
-                                 if args.exchange == "halo" else "all_gather_into_tensor")
-                               + f" over {args.dist_backend}"
-                               + (" (RCCL, xGMI)" if args.dist_backend == "nccl" else " (rehearsal)"))
-                if world > 1 else None,
-                "halo_bytes_per_step_rank0": (sum(ex.bytes_per_exchange for _, ex in exchanges64)
-                                              if exchanges64 else None),
-            },
-            "setup_ramp": {"ms": args.ramp_ms, "steps": ramp_steps,
-                           "note": "untimed steps before the warm-up so the GPU clocks reach steady "
-                                   "state; the timed region is exactly `steps` full steps"},
-            "hbm_gbps": round(hbm_gbs, 1),
+        extra = {
             "roofline": {
                 "bound": "hbm",
                 "kernel": ("rsp_k::spmv_tiles_batch<double,true,false,true>" if batches
@@ -832,11 +889,7 @@ def main():
             "per_matrix_us_rank0": per_matrix,
             "parity_check": "ok" if check_ok else "FAILED",
         }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    if not check_ok:
-        sys.exit(3)
+    return extra, check_ok
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ for r in $(seq 1 "${ROUNDS:-2}"); do
   i=0
   for lib in ${LIBS}; do
     i=$((i + 1))
-    RSP_PROBE_LIB=$PWD/$lib timeout -k 10 300 python bench.py --workload "${WORKLOAD:-moderate}" --no-cpu --steps 20 > "$O/l${i}_r$r.json" 2> "$O/l${i}_r$r.err" || { tail -20 "$O/l${i}_r$r.err"; exit 1; }
+    RSP_PROBE_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --workload "${WORKLOAD:-moderate}" --no-cpu --steps 20 > "$O/l${i}_r$r.json" 2> "$O/l${i}_r$r.err" || { tail -20 "$O/l${i}_r$r.err"; exit 1; }
     python3 - "$O/l${i}_r$r.json" "$lib" "$r" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

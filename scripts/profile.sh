@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 cd /tmp
 fatal() { if [ "$1" -ge 124 ]; then echo "STOP: $2 exited $1"; exit "$1"; fi; }
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
-    python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu > "$OUT/bench_prof.json" 2> "$OUT/stats.err"
+    python3 "$ROOT/bench.py" --full --steps 20 --warmup 3 --no-cpu > "$OUT/bench_prof.json" 2> "$OUT/stats.err"
 rc=$?; echo "stats rc=$rc"; fatal $rc stats
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- \
     python3 "$ROOT/scripts/pmc_run.py" --meta "$OUT/meta.json" > "$OUT/fetch.log" 2>&1

@@ -2,7 +2,7 @@
 # Round profiling session on the GPU box; every summary bench.py's roofline
 # cites comes from here (copy with scripts/collect_profiles.py):
 #   1. rocprofv3 --kernel-trace --stats on the DRIVER'S OWN bench command
-#      (python3 bench.py --gpus 1 --steps 20 --warmup 5: clock ramp, warm-up,
+#      (python3 bench.py --full --gpus 1 --steps 20 --warmup 5: clock ramp, warm-up,
 #      timed steps, config-5 Serena step, CPU baseline, all as the driver runs
 #      it) -> stats/ + bench_prof.json; scripts/check_roofline.py then checks
 #      that the rocprof average of spmv_tiles_batch<double> agrees with the
@@ -22,7 +22,7 @@ export TMPDIR=/tmp
 cd /tmp
 fatal() { if [ "$1" -ne 0 ]; then echo "STOP: $2 exited $1"; exit "$1"; fi; }
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
-    python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_prof.json" 2> "$OUT/stats.err"
+    python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_prof.json" 2> "$OUT/stats.err"
 rc=$?; echo "stats rc=$rc"; fatal $rc stats
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- \
     python3 "$ROOT/scripts/pmc_run.py" --meta "$OUT/meta.json" > "$OUT/fetch.log" 2>&1

@@ -9,7 +9,7 @@ T=${1:-r06}
 O=gpurun_out/${T}b
 mkdir -p "$O"
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || exit 1
+timeout -k 10 300 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || exit 1
 bash scripts/profile_round.sh $T || exit 1
-timeout -k 10 300 python bench.py --workload moderate --no-cpu > "$O/bench_moderate.json" 2> "$O/bench_moderate.err" || exit 1
+timeout -k 10 300 python bench.py --full --workload moderate --no-cpu > "$O/bench_moderate.json" 2> "$O/bench_moderate.err" || exit 1
 echo done

@@ -17,7 +17,7 @@ step() {  # name, limit, command...
     if [ $rc -ne 0 ]; then tail -20 "$OUT/$name.err"; exit $rc; fi
 }
 step pytest_gpu 900 python -m pytest tests -m gpu -q -rf -x
-step bench 600 python bench.py
-step bench_moderate 600 python bench.py --workload moderate --no-cpu
+step bench 600 python bench.py --full
+step bench_moderate 600 python bench.py --full --workload moderate --no-cpu
 step ilu 600 python scripts/bench_ilu0.py --json "$OUT/ilu.json"
 bash scripts/profile.sh "$TAG"

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 [ -n "${TESTS:-}" ] && { timeout -k 10 900 python -m pytest $TESTS -q -x -rf > "$O/pytest.log" 2>&1;
     rc=$?; tail -5 "$O/pytest.log"; [ $rc -eq 0 ] || exit $rc; }
 for r in $(seq 1 "${ROUNDS:-2}"); do for v in ${VARIANTS:-0 32}; do
-    RSP_SPMV_VARIANT=$v timeout -k 10 300 python bench.py --steps 30 --warmup 3 --no-cpu "$@" \
+    RSP_SPMV_VARIANT=$v timeout -k 10 300 python bench.py --full --steps 30 --warmup 3 --no-cpu "$@" \
         > "$O/v${v}_$r.json" 2> "$O/v${v}_$r.err" || { tail -20 "$O/v${v}_$r.err"; exit 1; }
     python - "$O/v${v}_$r.json" "v$v r$r" <<'PY'
 import json, sys

@@ -93,6 +93,36 @@ def test_bench_refuses_world_mismatch():
     assert r.returncode == 2 and "WORLD_SIZE is 1" in r.stderr
 
 
+class _S:
+    def __init__(self, name, y):
+        self.name, self.y64, self.m_local = name, y, y.numel() - 1  # one element of padding, as Slice.y64 may have
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy per matrix; whole while the set fits the
+    cap, else an equal share per matrix as the same sorted row sample in every
+    run; the files never exceed the cap."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "np", np)  # (the product modules load in the ranks only)
+    ys ={"a": torch.arange(1001, dtype=torch.float64), "b-1": torch.arange(41, dtype=torch.float64) * 0.5}
+    slices = [_S(n, y) for n, y in ys.items()]
+    bench.dump_outputs(str(tmp_path / "w"), slices, 0, 1)
+    for n, y in ys.items():
+        got = np.load(tmp_path / "w" / (n + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, y.numpy()[:-1])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 200)  # 100 rows per matrix
+    bench.dump_outputs(str(tmp_path / "s1"), slices, 0, 1)
+    bench.dump_outputs(str(tmp_path / "s2"), slices, 0, 1)
+    a1, a2 = np.load(tmp_path / "s1" / "a.npy"), np.load(tmp_path / "s2" / "a.npy")
+    assert a1.shape == (100,) and np.array_equal(a1, a2)
+    assert np.all(np.diff(a1) > 0) and a1.max() < 1000 and np.array_equal(a1, np.round(a1))  # distinct rows of y
+    assert np.array_equal(np.load(tmp_path / "s1" / "b-1.npy"), ys["b-1"].numpy()[:-1])  # fits: whole
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 8 * 200 + 2 * 128
+    bench.dump_outputs(str(tmp_path / "r"), slices[:1], 1, 2)  # N > 1: one file per rank
+    assert os.listdir(tmp_path / "r") == ["a.rank1.npy"]
+
+
 def _meta_worker(rank, world, port, names, q):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))

@@ -97,7 +97,7 @@ def test_bench_launches_n_ranks_itself():
     lets both ranks share cuda:0; the line must name 2 GPUs, the row-partitioned
     step's y must pass the oracle check, and with the product backend (nccl =
     RCCL) and too few GPUs bench.py must exit non-zero without a line."""
-    r = _bench("--gpus", "2", "--dist-backend", "gloo", "--workload", "Serena", "--steps", "3",
+    r = _bench("--full", "--gpus", "2", "--dist-backend", "gloo", "--workload", "Serena", "--steps", "3",
                "--warmup", "1", "--ramp-ms", "20", "--no-cpu", "--fp32-reps", "2")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -108,6 +108,32 @@ def test_bench_launches_n_ranks_itself():
     if torch.cuda.device_count() < 2:
         r = _bench("--gpus", "2", "--workload", "Serena", "--steps", "3", "--no-cpu", timeout=120)
         assert r.returncode != 0 and not r.stdout.strip() and "nccl" in r.stderr
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run prints the headline line only (no roofline, fp32, CPU
+    baseline or parity keys: those are --full's) and --dump-outputs writes each
+    matrix's y of the last timed step as float64, within the oracle's bound."""
+    names = ["G2_circuit", "ecology2"]
+    r = _bench("--gpus", "1", "--workload", ",".join(names), "--steps", "2", "--warmup", "1",
+               "--ramp-ms", "0", "--dump-outputs", str(tmp_path / "y"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GFLOP/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True
+    for k in ("roofline", "fp32", "cpu_baseline", "config5_serena", "per_matrix_calls", "parity_check"):
+        assert k not in d
+    assert sorted(os.listdir(tmp_path / "y")) == sorted(n + ".npy" for n in names)
+    for n in names:
+        A = csr.surrogate(n)
+        x, _ = csr.dlarnv(1, [0, 0, 0, 1], A.n)
+        y = np.load(tmp_path / "y" / (n + ".npy"))
+        assert y.dtype == np.float64 and y.shape == (A.n,)
+        ref = ob.spmv(A.rowptr, A.colidx, A.values, x)
+        assert np.all(np.abs(y - ref) <= ob.spmv_bound(A.rowptr, A.colidx, A.values, x, 2.0 ** -53))
 
 
 def test_ilu0_driver_reference_format():
