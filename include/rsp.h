@@ -230,6 +230,70 @@ rsp_status_t rsp_trsv_upper(rsp_handle_t handle, const void *alpha, rsp_ilu0_inf
                             rsp_datatype_t value_type, const void *d_values, const void *d_x,
                             void *d_y);
 
+/* --------------------------------- ILU(0)-preconditioned BiCGStab, dot */
+
+/* No single cuSPARSE call: this is the loop the csrilu02 + csrsv2 + SpMV call
+ * set is normally used in (an ILU-preconditioned Krylov solver), with the
+ * cuBLAS level-1 calls of that loop (cublasDdot / Daxpy / Dscal, and the
+ * cudaMemcpy of each scalar) replaced by fused kernels whose scalars stay on
+ * the device. Right-preconditioned BiCGStab, M = L U: L the unit lower part
+ * (rsp_trsv_lower_unit, op N), U the upper part with the diagonal
+ * (rsp_trsv_upper) of the factored values — the true ILU(0) apply, not the
+ * L L^T of GPU/ilu0.cu:296-302. Per iteration: two rsp_spmv, four triangular
+ * solves (alpha = 1, beta = 0) and five kernels of the solver's own (seven
+ * with a narrower preconditioner: its fp32 result is widened for the fp64
+ * SpMV). Deterministic: every dot product is summed in an order fixed by n,
+ * so equal inputs give bitwise equal x, iteration counts and histories. */
+typedef struct rsp_bicgstab *rsp_bicgstab_t;
+typedef enum { RSP_SOLVE_CONVERGED = 0, RSP_SOLVE_MAX_ITERS = 1, RSP_SOLVE_BREAKDOWN = 2 } rsp_solve_reason_t;
+
+/* A: square CSR (rows >= 1) with a schedule or plannable; its value type is
+ * the iteration type T (fp64 or fp32). info: an analysed ILU(0) info of A's
+ * pattern, or NULL = no preconditioner (M = I; precond_type and d_factor are
+ * then ignored). d_factor: the factored values (rsp_ilu0_factor output) in
+ * precond_type, which must not be wider than T; with fp32 under rsp_set_ftz(1)
+ * this is the fp32+FTZ preconditioner. Host-blocking: finishes the L and U
+ * solve plans and allocates all work vectors here, so solve plans and
+ * allocates nothing. A, info and d_factor must outlive the solver.
+ * INVALID_VALUE: a NULL argument, a non-square A, an un-analysed info,
+ * info's n != rows, precond_type wider than T. ZERO_PIVOT: rsp_ilu0_zero_pivot
+ * of info reports one (U divides by its diagonal). */
+rsp_status_t rsp_bicgstab_create(rsp_handle_t handle, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                 rsp_datatype_t precond_type, const void *d_factor, rsp_bicgstab_t *s);
+/* Solves A x = b. d_x: in = x0, out = the solution; d_b, d_x of type T, n
+ * elements, any 8-byte-aligned pointers. Stops when the recurrence residual
+ * meets ||r||_2 <= rtol ||b||_2 (rtol = 0: run max_iters), tested on the host
+ * every check_every iterations (>= 1; one asynchronous copy into pinned memory
+ * and one event wait — the only host wait of the loop) and after the last;
+ * check_every changes no bit of x for a given iteration count. Host-blocking.
+ * SUCCESS for all three reasons: *iters = iterations completed, *relres =
+ * ||r|| / ||b|| of the recurrence residual at the last check.
+ *   - b = 0: x = 0, 0 iterations, CONVERGED; an x0 that already meets rtol:
+ *     0 iterations, x untouched.
+ *   - BREAKDOWN: an iteration would have divided by a zero or non-finite rho,
+ *     omega, (rhat,v) or (t,t) (or b / x0 are not finite). Detected on the
+ *     device; x keeps the value of the last completed iteration, no NaN
+ *     reaches it. (t,t) == 0 exactly is the exact half step (s = 0): it is
+ *     taken with omega = 0 and is no breakdown.
+ * INVALID_VALUE: a NULL argument, max_iters < 0, check_every < 1, rtol < 0.
+ * EXECUTION_FAILED: cusparseXcsrsv2_zeroPivot's report for the L and U solves
+ * of this call, read once after the loop: a flow launch of one of them gave
+ * up a wait. The solver reuses its buffers every iteration, so the give-up
+ * recovery of rsp_trsv_zero_pivot (which re-runs recorded solves from their
+ * unchanged inputs) cannot apply here; x is then not a solution. */
+rsp_status_t rsp_bicgstab_solve(rsp_handle_t handle, rsp_bicgstab_t s, const void *d_b, void *d_x,
+                                double rtol, int max_iters, int check_every,
+                                int *iters, double *relres, rsp_solve_reason_t *reason);
+/* Relative residual after each checked iteration of the last solve: *count =
+ * how many there are, the first min(cap, *count) are written to relres. */
+rsp_status_t rsp_bicgstab_history(rsp_bicgstab_t s, int cap, double *relres, int *count);
+rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s);
+/* cublasDdot analogue on the solver's reduction: *result (HOST, fp64) =
+ * sum x_i y_i, products and sums in fp64 whatever value_type, in an order
+ * fixed by n (bitwise repeatable). Host-blocking. */
+rsp_status_t rsp_dot(rsp_handle_t handle, rsp_datatype_t value_type, int64_t n, const void *d_x,
+                     const void *d_y, double *result);
+
 /* ------------------------------------------------ multi-GPU halo exchange */
 
 /* Indexed gather dst[i] = src[idx[i]] for i < n (value_type elements). The

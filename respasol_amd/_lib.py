@@ -50,6 +50,16 @@ R_32F = 1
 OP_N = 0
 OP_T = 1
 
+SOLVE_CONVERGED = 0
+SOLVE_MAX_ITERS = 1
+SOLVE_BREAKDOWN = 2
+# Geometry of the Krylov kernels' reductions (rsp_kernels.h kKryChunk /
+# kKryMaxGrid): a workgroup sums KRY_CHUNK contiguous elements, and at most
+# KRY_MAX_GRID workgroups run (beyond KRY_CHUNK * KRY_MAX_GRID elements the
+# per-workgroup range grows by whole chunks instead).
+KRY_CHUNK = 2048
+KRY_MAX_GRID = 1024
+
 MM_FULL_SYMMETRIC = 0x1
 MM_QUIET = 0x2
 MM_SERIAL = 0x4
@@ -106,6 +116,11 @@ RSP_PROTOS = {
     "rsp_ilu0_levels": (i32, [vp, ip, ip]),
     "rsp_ilu0_solve_blocks": (i32, [vp, ip, ip]),
     "rsp_trsv_analysis": (i32, [vp, i32, vp]),
+    "rsp_bicgstab_create": (i32, [vp, vp, vp, i32, vp, C.POINTER(vp)]),
+    "rsp_bicgstab_solve": (i32, [vp, vp, vp, vp, C.c_double, i32, i32, ip, C.POINTER(C.c_double), ip]),
+    "rsp_bicgstab_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),
+    "rsp_bicgstab_destroy": (i32, [vp]),
+    "rsp_dot": (i32, [vp, i32, i64, vp, vp, C.POINTER(C.c_double)]),
     "rsp_gather": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_scatter": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_spmat_set_local_cols": (i32, [vp, i64]),

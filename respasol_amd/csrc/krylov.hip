@@ -1,0 +1,468 @@
+// krylov.hip — the vector side of the ILU(0)-preconditioned BiCGStab iteration
+// (rsp_bicgstab_*) and rsp_dot, for gfx950. The SpMVs and triangular solves of
+// an iteration are the library's existing entry points; everything between
+// them is here, five launches per iteration:
+//
+//   p_update   rho' = (rhat,r); beta = (rho'/rho)(alpha/omega); p = r + beta (p - omega v)
+//   dot_rhv    (rhat,v)
+//   s_update   alpha = rho'/(rhat,v); s = r - alpha v
+//   dot_ts     (t,s) and (t,t) in one pass
+//   x_update   omega = (t,s)/(t,t); x += alpha phat + omega shat; r = s - omega t;
+//              (rhat,r) and (r,r)
+//
+// Scalars stay on the device (rsp::kKry* slots of one fp64 block). A dot
+// leaves one partial per workgroup; the kernel that needs the scalar sums the
+// partials in its prologue — the launch boundary is the only synchronisation,
+// so there is no counter, no fence and no atomic accumulator, and the result
+// depends on n alone. Every workgroup derives the same scalar from the same
+// partials in the same order; workgroup 0 also stores it for later kernels,
+// into a slot that no workgroup of the same launch reads.
+//
+// Breakdown: a kernel that would divide by a zero or non-finite rho, omega,
+// (rhat,v) or (t,t) stores a code in kKryFlag and returns; every later kernel
+// returns on the code, so x, r and p keep their last good values. (t,t) == 0
+// with a finite (t,s) is t == 0, i.e. s == 0 up to A's null space: omega = 0
+// is taken (x += alpha phat, r = s), and the next iteration's omega check
+// reports the breakdown if r is not yet small.
+//
+// Element ownership: workgroup g owns [g * chunk, (g + 1) * chunk), thread t
+// the 16-byte groups t, t + 256, ... of it, in that order. Pointers that are
+// all 16-byte aligned move whole groups (double2 / float4); otherwise (an
+// 8-byte-aligned base) and in the tail the same elements move one by one, so
+// the summation order does not depend on the alignment.
+//
+// Compiled twice: namespace rsp_k (fp64 + fp32) and rsp_k_ftz (the fp32 and
+// fp32-copy forms, -fgpu-flush-denormals-to-zero), see rsp_kernels.h.
+
+#include <hip/hip_runtime.h>
+
+#include "rsp_kernels.h"
+
+#ifndef RSP_KNS
+#define RSP_KNS rsp_k
+#endif
+
+namespace RSP_KNS {
+
+using namespace rsp;
+
+namespace {
+
+template <typename T>
+struct Grp {
+    static constexpr int V = 16 / sizeof(T);
+    T e[V];
+};
+
+template <typename T, bool VEC>
+__device__ __forceinline__ Grp<T> ld(const T *p, long long j, int cnt) {
+    Grp<T> g;
+    if (VEC && cnt == Grp<T>::V) {
+        using V4 = __attribute__((ext_vector_type(4))) unsigned;
+        const V4 w = *reinterpret_cast<const V4 *>(p + j);
+        __builtin_memcpy(g.e, &w, 16);
+    } else {
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) g.e[k] = k < cnt ? p[j + k] : T(0);
+    }
+    return g;
+}
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void st(T *p, long long j, int cnt, const Grp<T> &g) {
+    if (VEC && cnt == Grp<T>::V) {
+        using V4 = __attribute__((ext_vector_type(4))) unsigned;
+        V4 w;
+        __builtin_memcpy(&w, g.e, 16);
+        *reinterpret_cast<V4 *>(p + j) = w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++)
+            if (k < cnt) p[j + k] = g.e[k];
+    }
+}
+
+// the fp32 copy of a double group (own allocation: 8-byte aligned at even j)
+template <bool VEC>
+__device__ __forceinline__ void st_copy32(float *p, long long j, int cnt, const Grp<double> &g) {
+    if (VEC && cnt == 2) {
+        *reinterpret_cast<float2 *>(p + j) = make_float2((float)g.e[0], (float)g.e[1]);
+    } else {
+        for (int k = 0; k < cnt; k++) p[j + k] = (float)g.e[k];
+    }
+}
+
+// Sum of one value per thread, the same in every thread: 64-lane down-tree,
+// then the four waves in order (rsp::kry_combine_host restates it).
+__device__ __forceinline__ double block_sum(double v, double *lds) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();  // lds free again
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+__device__ __forceinline__ double combine(const double *blk, int dot, double *lds) {
+    const double *part = blk + kKryScalars + (size_t)dot * kKryMaxGrid;
+    const int g = (int)gridDim.x;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < g; i += kKryThreads) v += part[i];
+    return block_sum(v, lds);
+}
+
+__device__ __forceinline__ void put_partial(double *blk, int dot, double v) {
+    if (threadIdx.x == 0) blk[kKryScalars + (size_t)dot * kKryMaxGrid + blockIdx.x] = v;
+}
+
+// The breakdown flag, the same for every thread of the workgroup (one thread
+// reads it: a workgroup of the launch that sets it may otherwise see it change
+// between two of its waves; such a workgroup derives the same breakdown from
+// the partials itself, so either value makes it return).
+__device__ __forceinline__ bool broken(const double *blk, double *lds) {
+    if (threadIdx.x == 0) lds[0] = blk[kKryFlag];
+    __syncthreads();
+    return lds[0] != 0.0;  // (block_sum synchronises before it writes lds again)
+}
+
+__device__ __forceinline__ bool bad_divisor(double d) { return d == 0.0 || !__builtin_isfinite(d); }
+
+__device__ __forceinline__ void set_break(double *blk, int code, int it) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        blk[kKryFlag] = (double)code;
+        blk[kKryFlagIt] = (double)it;
+    }
+}
+
+// the loop every kernel shares: thread t's groups of the workgroup's range
+#define KRY_FOR_GROUPS(T, n, chunk)                                                             \
+    const long long c0_ = (long long)blockIdx.x * (chunk);                                      \
+    const long long c1_ = c0_ + (chunk) < (n) ? c0_ + (chunk) : (n);                            \
+    for (long long j = c0_ + (long long)threadIdx.x * Grp<T>::V; j < c1_;                       \
+         j += (long long)kKryThreads * Grp<T>::V)                                               \
+        if (const int cnt = (int)(c1_ - j < Grp<T>::V ? c1_ - j : Grp<T>::V))
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_init(long long n, long long chunk, double *blk,
+                                                        const T *__restrict__ b, const T *__restrict__ v,
+                                                        T *__restrict__ r, T *__restrict__ rhat) {
+    __shared__ double lds[kKryThreads / 64];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        blk[kKryRho0] = 1.0;
+        blk[kKryRho1] = 1.0;
+        blk[kKryAlpha] = 1.0;
+        blk[kKryOmega] = 1.0;
+        blk[kKryFlag] = 0.0;
+        blk[kKryFlagIt] = 0.0;
+    }
+    double bb = 0.0, rr = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> gb = ld<T, VEC>(b, j, cnt), gv = ld<T, VEC>(v, j, cnt);
+        Grp<T> gr;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) {
+            gr.e[k] = gb.e[k] - gv.e[k];
+            if (k < cnt) {
+                bb += (double)gb.e[k] * (double)gb.e[k];
+                rr += (double)gr.e[k] * (double)gr.e[k];
+            }
+        }
+        st<T, VEC>(r, j, cnt, gr);
+        st<T, VEC>(rhat, j, cnt, gr);
+    }
+    bb = block_sum(bb, lds);
+    rr = block_sum(rr, lds);
+    put_partial(blk, kKryPartBB, bb);
+    put_partial(blk, kKryPartRR, rr);
+    put_partial(blk, kKryPartRhR, rr);
+}
+
+template <typename T, bool VEC, bool COPY>
+__global__ __launch_bounds__(kKryThreads) void kry_p_update(long long n, long long chunk, double *blk, int it,
+                                                            const T *__restrict__ r, const T *__restrict__ v,
+                                                            T *__restrict__ p, float *__restrict__ copy32) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    const double rho = combine(blk, kKryPartRhR, lds);
+    double beta = 0.0, omega = 0.0;
+    if (bad_divisor(rho)) {  // the next iteration's divisor (and this one's alpha would be 0)
+        set_break(blk, kKryBreakRho, it);
+        return;
+    }
+    if (it > 1) {
+        const double rho_old = blk[(it & 1) ? kKryRho0 : kKryRho1];
+        const double alpha = blk[kKryAlpha];
+        omega = blk[kKryOmega];
+        if (bad_divisor(rho_old)) {
+            set_break(blk, kKryBreakRho, it);
+            return;
+        }
+        if (bad_divisor(omega)) {
+            set_break(blk, kKryBreakOmega, it);
+            return;
+        }
+        beta = (rho / rho_old) * (alpha / omega);
+        if (!__builtin_isfinite(beta)) {
+            set_break(blk, kKryBreakRho, it);
+            return;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) blk[(it & 1) ? kKryRho1 : kKryRho0] = rho;
+    const T tb = (T)beta, tw = (T)omega;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> gp = ld<T, VEC>(r, j, cnt);
+        if (it > 1) {
+            const Grp<T> go = ld<T, VEC>(p, j, cnt), gv = ld<T, VEC>(v, j, cnt);
+#pragma unroll
+            for (int k = 0; k < Grp<T>::V; k++) gp.e[k] = gp.e[k] + tb * (go.e[k] - tw * gv.e[k]);
+        }
+        st<T, VEC>(p, j, cnt, gp);
+        if constexpr (COPY) st_copy32<VEC>(copy32, j, cnt, gp);
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_dot_rhv(long long n, long long chunk, double *blk,
+                                                           const T *__restrict__ rhat, const T *__restrict__ v) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    double acc = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> ga = ld<T, VEC>(rhat, j, cnt), gb = ld<T, VEC>(v, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++)
+            if (k < cnt) acc += (double)ga.e[k] * (double)gb.e[k];
+    }
+    put_partial(blk, kKryPartRhV, block_sum(acc, lds));
+}
+
+template <typename T, bool VEC, bool COPY>
+__global__ __launch_bounds__(kKryThreads) void kry_s_update(long long n, long long chunk, double *blk, int it,
+                                                            const T *__restrict__ r, const T *__restrict__ v,
+                                                            T *__restrict__ s, float *__restrict__ copy32) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    const double rhv = combine(blk, kKryPartRhV, lds);
+    if (bad_divisor(rhv)) {
+        set_break(blk, kKryBreakRhV, it);
+        return;
+    }
+    const double alpha = blk[(it & 1) ? kKryRho1 : kKryRho0] / rhv;
+    if (!__builtin_isfinite(alpha)) {
+        set_break(blk, kKryBreakRhV, it);
+        return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) blk[kKryAlpha] = alpha;
+    const T ta = (T)alpha;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> gr = ld<T, VEC>(r, j, cnt), gv = ld<T, VEC>(v, j, cnt);
+        Grp<T> gs;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) gs.e[k] = gr.e[k] - ta * gv.e[k];
+        st<T, VEC>(s, j, cnt, gs);
+        if constexpr (COPY) st_copy32<VEC>(copy32, j, cnt, gs);
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_dot_ts(long long n, long long chunk, double *blk,
+                                                          const T *__restrict__ t, const T *__restrict__ s) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    double ts = 0.0, tt = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> gt = ld<T, VEC>(t, j, cnt), gs = ld<T, VEC>(s, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++)
+            if (k < cnt) {
+                ts += (double)gt.e[k] * (double)gs.e[k];
+                tt += (double)gt.e[k] * (double)gt.e[k];
+            }
+    }
+    ts = block_sum(ts, lds);
+    tt = block_sum(tt, lds);
+    put_partial(blk, kKryPartTS, ts);
+    put_partial(blk, kKryPartTT, tt);
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_x_update(long long n, long long chunk, double *blk, int it,
+                                                            T *__restrict__ x, T *__restrict__ r,
+                                                            const T *__restrict__ rhat, const T *__restrict__ s,
+                                                            const T *__restrict__ t, const T *__restrict__ phat,
+                                                            const T *__restrict__ shat) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    const double ts = combine(blk, kKryPartTS, lds);
+    const double tt = combine(blk, kKryPartTT, lds);
+    if (!__builtin_isfinite(tt) || !__builtin_isfinite(ts)) {
+        set_break(blk, kKryBreakTT, it);
+        return;
+    }
+    const double omega = tt == 0.0 ? 0.0 : ts / tt;  // t == 0: the half step was exact (header)
+    if (!__builtin_isfinite(omega)) {
+        set_break(blk, kKryBreakTT, it);
+        return;
+    }
+    const double alpha = blk[kKryAlpha];
+    if (blockIdx.x == 0 && threadIdx.x == 0) blk[kKryOmega] = omega;
+    const T ta = (T)alpha, tw = (T)omega;
+    double rhr = 0.0, rr = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> gx = ld<T, VEC>(x, j, cnt);
+        const Grp<T> gp = ld<T, VEC>(phat, j, cnt), gh = ld<T, VEC>(shat, j, cnt);
+        const Grp<T> gs = ld<T, VEC>(s, j, cnt), gt = ld<T, VEC>(t, j, cnt), gq = ld<T, VEC>(rhat, j, cnt);
+        Grp<T> gr;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) {
+            gx.e[k] = (gx.e[k] + ta * gp.e[k]) + tw * gh.e[k];
+            gr.e[k] = gs.e[k] - tw * gt.e[k];
+            if (k < cnt) {
+                rhr += (double)gq.e[k] * (double)gr.e[k];
+                rr += (double)gr.e[k] * (double)gr.e[k];
+            }
+        }
+        st<T, VEC>(x, j, cnt, gx);
+        st<T, VEC>(r, j, cnt, gr);
+    }
+    rhr = block_sum(rhr, lds);
+    rr = block_sum(rr, lds);
+    put_partial(blk, kKryPartRhR, rhr);
+    put_partial(blk, kKryPartRR, rr);
+}
+
+// dst (fp64) = src (fp32); thread t's groups are float4 -> 2 x double2
+template <bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_widen(long long n, long long chunk, const double *blk,
+                                                         const float *__restrict__ src, double *__restrict__ dst) {
+    __shared__ double lds[1];
+    if (broken(blk, lds)) return;
+    KRY_FOR_GROUPS(float, n, chunk) {
+        const Grp<float> g = ld<float, VEC>(src, j, cnt);
+        Grp<double> lo, hi;
+        lo.e[0] = g.e[0];
+        lo.e[1] = g.e[1];
+        hi.e[0] = g.e[2];
+        hi.e[1] = g.e[3];
+        st<double, VEC>(dst, j, cnt < 2 ? cnt : 2, lo);
+        if (cnt > 2) st<double, VEC>(dst, j + 2, cnt - 2, hi);
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_zero(long long n, long long chunk, T *__restrict__ x) {
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> g;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) g.e[k] = T(0);
+        st<T, VEC>(x, j, cnt, g);
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void kry_dot(long long n, long long chunk, double *blk,
+                                                       const T *__restrict__ x, const T *__restrict__ y) {
+    __shared__ double lds[kKryThreads / 64];
+    double acc = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> ga = ld<T, VEC>(x, j, cnt), gb = ld<T, VEC>(y, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++)
+            if (k < cnt) acc += (double)ga.e[k] * (double)gb.e[k];
+    }
+    put_partial(blk, kKryPartRR, block_sum(acc, lds));
+}
+
+inline bool aligned16(std::initializer_list<const void *> ps) {
+    uintptr_t m = 0;
+    for (const void *p : ps) m |= (uintptr_t)p;
+    return (m & 15) == 0;
+}
+
+template <typename T, bool COPY>
+hipError_t launch(KryOp op, const KryArgs &a, hipStream_t s) {
+    const KryGrid kg = kry_grid(a.n);
+    const dim3 grid(kg.grid), block(kKryThreads);
+    const long long n = a.n, ch = kg.chunk;
+    const T *b = (const T *)a.b, *c = (const T *)a.c, *phat = (const T *)a.phat, *shat = (const T *)a.shat;
+    T *x = (T *)a.x, *r = (T *)a.r, *rhat = (T *)a.rhat, *p = (T *)a.p, *v = (T *)a.v, *sv = (T *)a.s,
+      *t = (T *)a.t;
+    float *c32 = (float *)a.copy32;
+#define KRY_LAUNCH(ALIGNED, KERN, KERN_U, ...)                                           \
+    do {                                                                                 \
+        if (ALIGNED)                                                                     \
+            hipLaunchKernelGGL(KERN, grid, block, 0, s, __VA_ARGS__);                    \
+        else                                                                             \
+            hipLaunchKernelGGL(KERN_U, grid, block, 0, s, __VA_ARGS__);                  \
+    } while (0)
+    switch (op) {
+        case kKryInit:
+            KRY_LAUNCH(aligned16({b, v, r, rhat}), (kry_init<T, true>), (kry_init<T, false>), n, ch, a.blk, b,
+                       (const T *)v, r, rhat);
+            break;
+        case kKryPUpdate:
+            KRY_LAUNCH(aligned16({r, v, p, c32}), (kry_p_update<T, true, COPY>), (kry_p_update<T, false, COPY>), n,
+                       ch, a.blk, a.it, (const T *)r, (const T *)v, p, c32);
+            break;
+        case kKryDotRhV:
+            KRY_LAUNCH(aligned16({rhat, v}), (kry_dot_rhv<T, true>), (kry_dot_rhv<T, false>), n, ch, a.blk,
+                       (const T *)rhat, (const T *)v);
+            break;
+        case kKrySUpdate:
+            KRY_LAUNCH(aligned16({r, v, sv, c32}), (kry_s_update<T, true, COPY>), (kry_s_update<T, false, COPY>), n,
+                       ch, a.blk, a.it, (const T *)r, (const T *)v, sv, c32);
+            break;
+        case kKryDotTS:
+            KRY_LAUNCH(aligned16({t, sv}), (kry_dot_ts<T, true>), (kry_dot_ts<T, false>), n, ch, a.blk,
+                       (const T *)t, (const T *)sv);
+            break;
+        case kKryXUpdate:
+            KRY_LAUNCH(aligned16({x, r, rhat, sv, t, phat, shat}), (kry_x_update<T, true>),
+                       (kry_x_update<T, false>), n, ch, a.blk, a.it, x, r, (const T *)rhat, (const T *)sv,
+                       (const T *)t, phat, shat);
+            break;
+        case kKryZero:
+            KRY_LAUNCH(aligned16({x}), (kry_zero<T, true>), (kry_zero<T, false>), n, ch, x);
+            break;
+        case kKryDot:
+            KRY_LAUNCH(aligned16({b, c}), (kry_dot<T, true>), (kry_dot<T, false>), n, ch, a.blk, b, c);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+#undef KRY_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t krylov(KryOp op, int type, const KryArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (op == kKryWiden) {
+        const KryGrid kg = kry_grid(a.n);
+        if (aligned16({a.b, a.copy32}))
+            hipLaunchKernelGGL((kry_widen<true>), dim3(kg.grid), dim3(kKryThreads), 0, s, a.n, kg.chunk,
+                               (const double *)a.blk, (const float *)a.b, (double *)a.copy32);
+        else
+            hipLaunchKernelGGL((kry_widen<false>), dim3(kg.grid), dim3(kKryThreads), 0, s, a.n, kg.chunk,
+                               (const double *)a.blk, (const float *)a.b, (double *)a.copy32);
+        return hipGetLastError();
+    }
+    switch (type) {
+        case kKryF32: return launch<float, false>(op, a, s);
+        case kKryF64Copy32: return launch<double, true>(op, a, s);
+#ifndef RSP_FTZ_BUILD
+        case kKryF64: return launch<double, false>(op, a, s);
+#endif
+        default: return hipErrorInvalidValue;
+    }
+}
+
+void warm_krylov() {
+    hipFuncAttributes at;
+    (void)hipFuncGetAttributes(&at, reinterpret_cast<const void *>(kry_dot<float, true>));
+    int o = 0;  // (the use that loads the code object, as warm_spmv)
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kry_dot<float, true>, kKryThreads, 0);
+}
+
+}  // namespace RSP_KNS

@@ -8,11 +8,13 @@
 
 #include <hip/hip_runtime.h>
 #include <limits.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <unordered_map>
 #include <memory>
@@ -42,6 +44,10 @@ struct rsp_context {
     // on the handle's device on first use, freed by rsp_destroy
     unsigned long long *d_ftrace;
     unsigned long long *d_strace;
+    // rsp_dot: a Krylov block (rsp::kKryBlockDoubles) and its pinned mirror of
+    // the partials, allocated on first use, freed by rsp_destroy
+    double *d_dot;
+    double *h_dot;
 };
 
 // The SpMV schedule lives in device memory owned by the matrix descriptor
@@ -249,20 +255,26 @@ rsp_status_t rsp_create(rsp_handle_t *handle) {
     rsp_k::warm_ilu();
     rsp_k_ftz::warm_ilu();
     rsp_k::warm_analysis();
+    rsp_k::warm_krylov();
+    rsp_k_ftz::warm_krylov();
     c->d_ftrace = nullptr;
     c->d_strace = nullptr;
+    c->d_dot = nullptr;
+    c->h_dot = nullptr;
     *handle = c;
     return RSP_STATUS_SUCCESS;
 }
 
 rsp_status_t rsp_destroy(rsp_handle_t h) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
-    if (h->d_ftrace || h->d_strace) {
+    if (h->d_ftrace || h->d_strace || h->d_dot || h->h_dot) {
         int cur = 0;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(h->device);
         if (h->d_ftrace) (void)hipFree(h->d_ftrace);
         if (h->d_strace) (void)hipFree(h->d_strace);
+        if (h->d_dot) (void)hipFree(h->d_dot);
+        if (h->h_dot) (void)hipHostFree(h->h_dot);
         (void)hipSetDevice(cur);
     }
     delete h;
@@ -2624,6 +2636,279 @@ static rsp_status_t rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_i
 }
 
 
+/* ------------------------------------------------------ BiCGStab + dot */
+
+// One solver: the work vectors (one allocation), the scalar / partial block
+// and the pinned mirror the convergence read-back lands in.
+struct rsp_bicgstab {
+    int device = 0;
+    rsp_spmat_t A = nullptr;
+    rsp_ilu0_info_t info = nullptr;  // null: M = I
+    rsp_datatype_t T = RSP_R_64F, P = RSP_R_64F;
+    const void *factor = nullptr;
+    long long n = 0;
+    void *d_arena = nullptr;
+    void *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *s = nullptr, *t = nullptr;
+    void *phat = nullptr, *shat = nullptr;  // type T (M = I: p and s themselves)
+    void *pin = nullptr, *pmid = nullptr, *pout = nullptr;  // the preconditioner's input / L result / U result (type P)
+    double *d_blk = nullptr;
+    double *h_pin = nullptr;  // kKryScalars + 2 kKryMaxGrid doubles
+    hipEvent_t ev = nullptr;
+    std::vector<double> history;
+    bool mixed() const { return info && P != T; }
+};
+
+static void bicgstab_free(rsp_bicgstab *s) {
+    if (!s) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(s->device);
+    if (s->d_arena) (void)hipFree(s->d_arena);
+    if (s->h_pin) (void)hipHostFree(s->h_pin);
+    if (s->ev) (void)hipEventDestroy(s->ev);
+    (void)hipSetDevice(cur);
+    delete s;
+}
+
+static rsp_status_t rsp_bicgstab_create_impl(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                             rsp_datatype_t precond_type, const void *d_factor,
+                                             rsp_bicgstab_t *out, rsp_bicgstab *&s) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!out) return RSP_STATUS_INVALID_VALUE;
+    *out = nullptr;
+    if (!A || A->rows != A->cols || A->rows < 1) return RSP_STATUS_INVALID_VALUE;
+    if (info) {
+        if (precond_type != RSP_R_64F && precond_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+        if (!info->analysed || info->n != A->rows || !d_factor) return RSP_STATUS_INVALID_VALUE;
+        if (A->type == RSP_R_32F && precond_type == RSP_R_64F) return RSP_STATUS_INVALID_VALUE;
+    }
+    if (!A->planned || A->plan_type != A->type) {
+        const rsp_status_t st = spmv_plan(h, A, A->type);
+        if (st != RSP_STATUS_SUCCESS) return st;
+    }
+    if (info) {
+        rsp_status_t st = ilu_solves_ready(h, info);
+        if (st == RSP_STATUS_SUCCESS) st = ilu_plan_u(h, info);
+        if (st != RSP_STATUS_SUCCESS) return st;
+        int pos = -1;
+        st = rsp_ilu0_zero_pivot(h, info, &pos);  // U divides by its diagonal
+        if (st != RSP_STATUS_SUCCESS) return st;
+    }
+    s = new rsp_bicgstab;
+    s->device = h->device;
+    s->A = A;
+    s->info = info;
+    s->T = A->type;
+    s->P = info ? precond_type : A->type;
+    s->factor = d_factor;
+    s->n = A->rows;
+    const size_t tb = align256((size_t)s->n * elem_size(s->T)), pb = align256((size_t)s->n * elem_size(s->P));
+    const size_t blk = align256(rsp::kKryBlockDoubles * sizeof(double));
+    // r, rhat, p, v, s, t; with M: phat, shat (T) and the apply's vectors (P)
+    const int nt = info ? 8 : 6, np = !info ? 0 : (s->mixed() ? 3 : 1);
+    RSP_CHECK_HIP(hipMalloc(&s->d_arena, blk + nt * tb + np * pb));
+    char *at = (char *)s->d_arena;
+    s->d_blk = (double *)at;
+    at += blk;
+    void **tv[] = {&s->r, &s->rhat, &s->p, &s->v, &s->s, &s->t, &s->phat, &s->shat};
+    for (int k = 0; k < nt; k++, at += tb) *tv[k] = at;
+    if (!info) {
+        s->phat = s->p;
+        s->shat = s->s;
+    } else if (s->mixed()) {
+        s->pin = at;
+        s->pmid = at + pb;
+        s->pout = at + 2 * pb;
+    } else {
+        s->pmid = at;
+    }
+    RSP_CHECK_HIP(hipHostMalloc((void **)&s->h_pin, (rsp::kKryScalars + 2 * (size_t)rsp::kKryMaxGrid) * sizeof(double),
+                                hipHostMallocDefault));
+    RSP_CHECK_HIP(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    *out = s;
+    s = nullptr;
+    return RSP_STATUS_SUCCESS;
+}
+
+// z = M^-1 y with M = L U: y -> L -> pmid -> U -> z; in mixed mode y's fp32
+// copy (written by the kernel that made y) is the input and the fp32 result
+// is widened into z for the fp64 SpMV.
+static rsp_status_t bicgstab_apply(rsp_handle_t h, rsp_bicgstab *s, const void *y, void *z, bool ftz) {
+    const double one_d = 1.0;
+    const float one_f = 1.0f;
+    const void *one = s->P == RSP_R_64F ? (const void *)&one_d : (const void *)&one_f;
+    const void *in = s->mixed() ? s->pin : y;
+    void *res = s->mixed() ? s->pout : z;
+    rsp_status_t st = rsp_trsv_lower_unit_impl(h, RSP_OPERATION_NON_TRANSPOSE, one, s->info, s->P, s->factor, in,
+                                               s->pmid, true);
+    if (st != RSP_STATUS_SUCCESS) return st;
+    st = rsp_trsv_upper_impl(h, one, s->info, s->P, s->factor, s->pmid, res, true);
+    if (st != RSP_STATUS_SUCCESS || !s->mixed()) return st;
+    rsp::KryArgs a{};
+    a.n = s->n;
+    a.blk = s->d_blk;
+    a.b = res;
+    a.copy32 = z;
+    const hipError_t e = ftz ? rsp_k_ftz::krylov(rsp::kKryWiden, rsp::kKryF64Copy32, a, h->stream)
+                             : rsp_k::krylov(rsp::kKryWiden, rsp::kKryF64Copy32, a, h->stream);
+    return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+}
+
+static rsp_status_t rsp_bicgstab_solve_impl(rsp_handle_t h, rsp_bicgstab_t s, const void *d_b, void *d_x,
+                                            double rtol, int max_iters, int check_every, int *iters,
+                                            double *relres, rsp_solve_reason_t *reason) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!s || !d_b || !d_x || !iters || !relres || !reason) return RSP_STATUS_INVALID_VALUE;
+    if (max_iters < 0 || check_every < 1 || !(rtol >= 0.0)) return RSP_STATUS_INVALID_VALUE;
+    *iters = 0;
+    *relres = 0.0;
+    *reason = RSP_SOLVE_MAX_ITERS;
+    s->history.clear();
+    s->history.reserve((size_t)max_iters / check_every + 2);
+    const int type = s->T == RSP_R_32F ? rsp::kKryF32 : (s->mixed() ? rsp::kKryF64Copy32 : rsp::kKryF64);
+    const bool ftz = h->ftz != 0 && type != rsp::kKryF64;
+    const int G = rsp::kry_grid(s->n).grid;
+    const double one_d = 1.0, zero_d = 0.0;
+    const float one_f = 1.0f, zero_f = 0.0f;
+    const void *one = s->T == RSP_R_64F ? (const void *)&one_d : (const void *)&one_f;
+    const void *zero = s->T == RSP_R_64F ? (const void *)&zero_d : (const void *)&zero_f;
+    rsp::KryArgs a{};
+    a.n = s->n;
+    a.blk = s->d_blk;
+    a.b = d_b;
+    a.x = d_x;
+    a.r = s->r;
+    a.rhat = s->rhat;
+    a.p = s->p;
+    a.v = s->v;
+    a.s = s->s;
+    a.t = s->t;
+    a.phat = s->phat;
+    a.shat = s->shat;
+    a.copy32 = s->mixed() ? s->pin : nullptr;
+    auto kern = [&](rsp::KryOp op) {
+        const hipError_t e = ftz ? rsp_k_ftz::krylov(op, type, a, h->stream) : rsp_k::krylov(op, type, a, h->stream);
+        return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+    };
+    auto spmv = [&](const void *x, void *y) {
+        return spmv_run(h, RSP_OPERATION_NON_TRANSPOSE, one, s->A, x, zero, y, s->T, nullptr, 0);
+    };
+    // the one host wait of an iteration: scalars + the (r,r) partials, one
+    // async copy into the pinned mirror, one event
+    double *hp = s->h_pin;
+    auto read_back = [&]() -> rsp_status_t {
+        RSP_CHECK_HIP(hipMemcpyAsync(hp, s->d_blk, (rsp::kKryScalars + (size_t)G) * sizeof(double),
+                                     hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipEventRecord(s->ev, h->stream));
+        RSP_CHECK_HIP(hipEventSynchronize(s->ev));
+        return RSP_STATUS_SUCCESS;
+    };
+    const int gen0[2] = {s->info ? s->info->solve_gen[RSP_TRSV_L] : 0, s->info ? s->info->solve_gen[RSP_TRSV_U] : 0};
+#define RSP_TRY(call)                                   \
+    do {                                                \
+        const rsp_status_t st_ = (call);                \
+        if (st_ != RSP_STATUS_SUCCESS) return st_;      \
+    } while (0)
+    // r = b - A x0, rhat = r, (b,b), (r,r)
+    RSP_TRY(spmv(d_x, s->v));
+    RSP_TRY(kern(rsp::kKryInit));
+    RSP_CHECK_HIP(hipMemcpyAsync(hp + rsp::kKryScalars + rsp::kKryMaxGrid,
+                                 s->d_blk + rsp::kKryScalars + (size_t)rsp::kKryPartBB * rsp::kKryMaxGrid,
+                                 (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RSP_TRY(read_back());
+    const double bb = rsp::kry_combine_host(hp + rsp::kKryScalars + rsp::kKryMaxGrid, G);
+    double rr = rsp::kry_combine_host(hp + rsp::kKryScalars, G);
+    const double bnorm = sqrt(bb);
+    if (bb == 0.0) {  // x = 0 solves it
+        RSP_TRY(kern(rsp::kKryZero));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        *reason = RSP_SOLVE_CONVERGED;
+        return RSP_STATUS_SUCCESS;
+    }
+    if (!std::isfinite(bb) || !std::isfinite(rr)) {  // b or x0 not finite: nothing to iterate on
+        *relres = sqrt(rr) / bnorm;
+        *reason = RSP_SOLVE_BREAKDOWN;
+        return RSP_STATUS_SUCCESS;
+    }
+    double rel = sqrt(rr) / bnorm;
+    *relres = rel;
+    int done = 0;
+    if (rel <= rtol) {
+        *reason = RSP_SOLVE_CONVERGED;
+    } else {
+        for (int it = 1; it <= max_iters; it++) {
+            a.it = it;
+            RSP_TRY(kern(rsp::kKryPUpdate));
+            if (s->info) RSP_TRY(bicgstab_apply(h, s, s->p, s->phat, ftz));
+            RSP_TRY(spmv(s->phat, s->v));
+            RSP_TRY(kern(rsp::kKryDotRhV));
+            RSP_TRY(kern(rsp::kKrySUpdate));
+            if (s->info) RSP_TRY(bicgstab_apply(h, s, s->s, s->shat, ftz));
+            RSP_TRY(spmv(s->shat, s->t));
+            RSP_TRY(kern(rsp::kKryDotTS));
+            RSP_TRY(kern(rsp::kKryXUpdate));
+            done = it;
+            if (it % check_every != 0 && it != max_iters) continue;
+            RSP_TRY(read_back());
+            rr = rsp::kry_combine_host(hp + rsp::kKryScalars, G);
+            rel = sqrt(rr) / bnorm;
+            const int flag = (int)hp[rsp::kKryFlag];
+            if (flag) done = (int)hp[rsp::kKryFlagIt] - 1;  // x, r and p stand as that iteration found them
+            s->history.push_back(rel);
+            if (rel <= rtol) {
+                *reason = RSP_SOLVE_CONVERGED;
+                break;
+            }
+            if (flag) {
+                *reason = RSP_SOLVE_BREAKDOWN;
+                break;
+            }
+        }
+    }
+#undef RSP_TRY
+    *iters = done;
+    *relres = rel;
+    if (s->info && done > 0) {
+        // cusparseXcsrsv2_zeroPivot of the L and U solves, for every apply of
+        // this call at once: a flow launch that gave up a wait left its
+        // generation in the solve's status word. The solver's buffers are
+        // reused every iteration, so the recovery of rsp_trsv_zero_pivot
+        // (re-running the recorded solves) cannot apply: reported.
+        int z[5];
+        RSP_CHECK_HIP(hipMemcpyAsync(z, s->info->d_zero, sizeof(z), hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        if (z[2 + RSP_TRSV_L] > gen0[0] || z[2 + RSP_TRSV_U] > gen0[1]) return RSP_STATUS_EXECUTION_FAILED;
+    }
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t rsp_dot_impl(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, const void *d_x,
+                                 const void *d_y, double *result) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (value_type != RSP_R_64F && value_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+    if (!result || n < 0 || (n > 0 && (!d_x || !d_y))) return RSP_STATUS_INVALID_VALUE;
+    *result = 0.0;
+    if (n == 0) return RSP_STATUS_SUCCESS;
+    if (!h->d_dot) RSP_CHECK_HIP(hipMalloc((void **)&h->d_dot, rsp::kKryBlockDoubles * sizeof(double)));
+    if (!h->h_dot)
+        RSP_CHECK_HIP(hipHostMalloc((void **)&h->h_dot, rsp::kKryMaxGrid * sizeof(double), hipHostMallocDefault));
+    rsp::KryArgs a{};
+    a.n = n;
+    a.blk = h->d_dot;
+    a.b = d_x;
+    a.c = d_y;
+    const int type = value_type == RSP_R_64F ? rsp::kKryF64 : rsp::kKryF32;
+    const hipError_t e = (h->ftz && type == rsp::kKryF32) ? rsp_k_ftz::krylov(rsp::kKryDot, type, a, h->stream)
+                                                          : rsp_k::krylov(rsp::kKryDot, type, a, h->stream);
+    if (e != hipSuccess) return RSP_STATUS_EXECUTION_FAILED;
+    const int G = rsp::kry_grid(n).grid;
+    RSP_CHECK_HIP(hipMemcpyAsync(h->h_dot, h->d_dot + rsp::kKryScalars + (size_t)rsp::kKryPartRR * rsp::kKryMaxGrid,
+                                 (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+    *result = rsp::kry_combine_host(h->h_dot, G);
+    return RSP_STATUS_SUCCESS;
+}
+
 }  // extern "C"
 
 // C-ABI entry points never let a C++ exception out (std::bad_alloc from the
@@ -2717,6 +3002,42 @@ rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_in
                                 int64_t *entries_staged) {
     return guarded([&] { return rsp_spmv_plan_host_impl(m, row_offsets, col_ind, nnz, compute_type, tiles,
                                                         entries_16bit, entries_staged); }, [] {});
+}
+
+rsp_status_t rsp_bicgstab_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                 rsp_datatype_t precond_type, const void *d_factor, rsp_bicgstab_t *s) {
+    rsp_bicgstab *made = nullptr;  // freed here unless create handed it over
+    const rsp_status_t st = guarded([&] { return rsp_bicgstab_create_impl(h, A, info, precond_type, d_factor, s, made); }, [] {});
+    bicgstab_free(made);
+    return st;
+}
+
+rsp_status_t rsp_bicgstab_solve(rsp_handle_t h, rsp_bicgstab_t s, const void *d_b, void *d_x, double rtol,
+                                int max_iters, int check_every, int *iters, double *relres,
+                                rsp_solve_reason_t *reason) {
+    return guarded([&] { return rsp_bicgstab_solve_impl(h, s, d_b, d_x, rtol, max_iters, check_every, iters, relres, reason); }, [] {});
+}
+
+rsp_status_t rsp_bicgstab_history(rsp_bicgstab_t s, int cap, double *relres, int *count) {
+    return guarded([&] {
+        if (!s || !count || cap < 0 || (cap > 0 && !relres)) return RSP_STATUS_INVALID_VALUE;
+        *count = (int)s->history.size();
+        for (int k = 0; k < cap && k < *count; k++) relres[k] = s->history[k];
+        return RSP_STATUS_SUCCESS;
+    }, [] {});
+}
+
+rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s) {
+    return guarded([&] {
+        if (!s) return RSP_STATUS_INVALID_VALUE;
+        bicgstab_free(s);
+        return RSP_STATUS_SUCCESS;
+    }, [] {});
+}
+
+rsp_status_t rsp_dot(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, const void *d_x, const void *d_y,
+                     double *result) {
+    return guarded([&] { return rsp_dot_impl(h, value_type, n, d_x, d_y, result); }, [] {});
 }
 
 }  // extern "C"

@@ -487,6 +487,84 @@ struct TrsvArgs {
     int flow_sleep;             // flow polls: longest pause, s_sleep units (RSP_ILU_FLOW_SLEEP)
 };
 
+
+// Krylov vector kernels (krylov.hip): the solver's own side of a BiCGStab
+// iteration (rsp_bicgstab_*) and rsp_dot. Every kernel runs kry_grid(n)
+// workgroups of kKryThreads threads; workgroup g owns the contiguous elements
+// [g * chunk, min(n, (g + 1) * chunk)), so the grid and every summation order
+// are functions of n alone. A dot leaves one fp64 partial per workgroup
+// (plain stores); the next kernel that needs the scalar sums the partials in
+// its prologue, every workgroup the same way (kry_combine_host restates that
+// order on the host).
+constexpr int kKryThreads = 256;
+constexpr int kKryChunk = 2048;    // elements per workgroup while the grid is below kKryMaxGrid
+constexpr int kKryMaxGrid = 1024;  // partials per dot
+struct KryGrid {
+    int grid;
+    long long chunk;  // a multiple of kKryChunk
+};
+inline KryGrid kry_grid(long long n) {
+    KryGrid g;
+    const long long span = (long long)kKryChunk * kKryMaxGrid;
+    g.chunk = (long long)kKryChunk * (n > span ? (n + span - 1) / span : 1);
+    g.grid = n > 0 ? (int)((n + g.chunk - 1) / g.chunk) : 1;
+    return g;
+}
+// The solver's device block, all fp64: kKryScalars scalars, then kKryDots
+// partial arrays of kKryMaxGrid entries each.
+enum {
+    kKryRho0 = 0,   // rho of the iterations of parity 0 / 1: a kernel reads the
+    kKryRho1 = 1,   // other parity's and writes its own, never one slot both ways
+    kKryAlpha = 2,
+    kKryOmega = 3,
+    kKryFlag = 4,   // 0, or the breakdown code (kKryBreak*): set once, every later kernel returns on it
+    kKryFlagIt = 5, // the iteration that set it
+    kKryScalars = 16
+};
+enum { kKryPartRR = 0, kKryPartBB, kKryPartRhR, kKryPartRhV, kKryPartTS, kKryPartTT, kKryDots };
+enum { kKryBreakRho = 1, kKryBreakOmega = 2, kKryBreakRhV = 3, kKryBreakTT = 4 };
+constexpr size_t kKryBlockDoubles = kKryScalars + (size_t)kKryDots * kKryMaxGrid;
+enum KryOp {
+    kKryInit,     // r = b - v (v = A x0), rhat = r; partials (b,b), (r,r), (rhat,r); scalars reset
+    kKryPUpdate,  // rho' from (rhat,r); beta; p = r + beta (p - omega v)  [+ fp32 copy]
+    kKryDotRhV,   // (rhat,v)
+    kKrySUpdate,  // alpha = rho' / (rhat,v); s = r - alpha v  [+ fp32 copy]
+    kKryDotTS,    // (t,s) and (t,t), one pass
+    kKryXUpdate,  // omega = (t,s)/(t,t); x += alpha phat + omega shat; r = s - omega t; (rhat,r), (r,r)
+    kKryWiden,    // dst (fp64) = src (fp32): the preconditioner's result for the fp64 SpMV
+    kKryZero,     // x = 0
+    kKryDot       // partials[kKryPartRR] of (x, y): rsp_dot
+};
+// type codes: the iteration type, and whether p / s get an fp32 copy
+enum { kKryF64 = 0, kKryF32 = 1, kKryF64Copy32 = 2 };
+struct KryArgs {
+    long long n;
+    double *blk;      // kKryBlockDoubles
+    int it;           // iteration (1-based): rho parity, first = no beta term
+    const void *b;    // kKryInit; kKryDot: x; kKryWiden: src
+    const void *c;    // kKryDot: y
+    void *x, *r, *rhat, *p, *v, *s, *t;
+    const void *phat, *shat;
+    void *copy32;     // kKryF64Copy32: the fp32 copy of p / s; kKryWiden: dst (fp64)
+};
+// kry_combine_host: the device's sum of g partials, restated: thread t adds
+// part[t], part[t + 256], ... in that order, then the 64-lane down-tree
+// (offsets 32 .. 1) and the four waves in order.
+inline double kry_combine_host(const double *part, int g) {
+    double v[kKryThreads];
+    for (int t = 0; t < kKryThreads; t++) {
+        v[t] = 0.0;
+        for (int i = t; i < g; i += kKryThreads) v[t] += part[i];
+    }
+    double w[kKryThreads / 64];
+    for (int k = 0; k < kKryThreads / 64; k++) {
+        double *l = v + 64 * k;
+        for (int off = 32; off > 0; off >>= 1)
+            for (int i = 0; i < off; i++) l[i] += l[i + off];
+        w[k] = l[0];
+    }
+    return ((w[0] + w[1]) + w[2]) + w[3];
+}
 }  // namespace rsp
 
 #define RSP_DECLARE_KERNEL_API(NS)                                                              \
@@ -500,6 +578,8 @@ struct TrsvArgs {
     hipError_t trsv_blocks_f32(const rsp::BlkArgs &a, hipStream_t s);                           \
     void warm_spmv();                                                                           \
     void warm_ilu();                                                                            \
+    hipError_t krylov(rsp::KryOp op, int type, const rsp::KryArgs &a, hipStream_t s);           \
+    void warm_krylov();                                                                         \
     }
 
 RSP_DECLARE_KERNEL_API(rsp_k)

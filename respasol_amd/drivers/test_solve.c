@@ -1,0 +1,210 @@
+/*
+ * test_solve.c — ILU(0)-preconditioned BiCGStab driver (built as `test_solve`).
+ * No GPU counterpart in the reference; shaped like its direct-solver drivers
+ * (Pardiso/test_pardiso.c): b = 1 (:107), solve, relative residual ||b - A x||
+ * / ||b|| recomputed on the host (:258-274).
+ *
+ *   test_solve <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32]
+ *              [--precond=fp64|fp32|none] [--ftz] [--rtol=R] [--maxit=N]
+ *              [--full-symmetric] [--dump=FILE]
+ *
+ * Flow: load as test_ilu0 does (outputbase 0); iteration values in --prec;
+ * b = 1, x0 = 0; [timed "Symbolic"] ILU analysis; [timed "Numeric"]
+ * factorisation of a copy of the values in the --precond type (default: the
+ * --prec type; must not be wider); [timed "Solve"] rsp_bicgstab_solve; the
+ * six-line report. Symbolic is wall-clock, Numeric and Solve are event pairs
+ * on the stream. The residual line is the TRUE residual, in fp64 on the host
+ * (rsp_host_spmv_f64 on the file's fp64 values), not the recurrence's.
+ * Exit 0 for any reason code (converged, max iterations, breakdown);
+ * non-zero only on a status error. --dump writes x (binary, --prec type).
+ */
+#include <hip/hip_runtime_api.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "drv_common.h"
+#include "rsp.h"
+#include "rsp_host.h"
+
+#define HIP_OR_FAIL(stat)                                                                       \
+    do {                                                                                        \
+        hipError_t s_ = (stat);                                                                 \
+        if (s_ != hipSuccess) {                                                                 \
+            fprintf(stderr, "HIP Error: %s %s %d\n", hipGetErrorString(s_), __FILE__, __LINE__); \
+            return 1;                                                                           \
+        }                                                                                       \
+    } while (0)
+#define RSP_OR_FAIL(stat)                                                                       \
+    do {                                                                                        \
+        rsp_status_t s_ = (stat);                                                               \
+        if (s_ != RSP_STATUS_SUCCESS) {                                                         \
+            fprintf(stderr, "RSP Error: %d (%s) %s %d\n", (int)s_, rsp_get_error_string(s_),    \
+                    __FILE__, __LINE__);                                                        \
+            return 1;                                                                           \
+        }                                                                                       \
+    } while (0)
+
+static void demote(void *dst, const double *src, size_t n, int fp32) {
+    for (size_t k = 0; k < n; k++) {
+        if (fp32)
+            ((float *)dst)[k] = (float)src[k];
+        else
+            ((double *)dst)[k] = src[k];
+    }
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) {
+        fprintf(stderr,
+                "-- Usage --\n"
+                "  %s <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32] [--precond=fp64|fp32|none]\n"
+                "     [--ftz] [--rtol=R] [--maxit=N] [--full-symmetric] [--dump=FILE]\n"
+                "  solves A x = 1 from x0 = 0 by ILU(0)-preconditioned BiCGStab.\n"
+                "  A symmetric file loads as its lower triangle unless --full-symmetric is given.\n",
+                argv[0]);
+        return 2;
+    }
+    const char *prec = drv_flag(argc, argv, 2, "prec");
+    const char *precond = drv_flag(argc, argv, 2, "precond");
+    const char *dump = drv_flag(argc, argv, 2, "dump");
+    const char *rtol_s = drv_flag(argc, argv, 2, "rtol");
+    const char *maxit_s = drv_flag(argc, argv, 2, "maxit");
+    const int fp32 = prec && strcmp(prec, "fp32") == 0;
+    const int ftz = drv_flag(argc, argv, 2, "ftz") != NULL;
+    const int fullsym = drv_flag(argc, argv, 2, "full-symmetric") != NULL;
+    const int use_m = !(precond && strcmp(precond, "none") == 0);
+    const int m32 = precond && *precond && use_m ? strcmp(precond, "fp32") == 0 : fp32;
+    const double rtol = rtol_s && *rtol_s ? atof(rtol_s) : (fp32 ? 1e-4 : 1e-10);
+    const int maxit = maxit_s && *maxit_s ? atoi(maxit_s) : 1000;
+    if (use_m && fp32 && !m32) {
+        fprintf(stderr, "Error: --precond=fp64 is wider than --prec=fp32\n");
+        return 2;
+    }
+
+    CSR A;
+    if (!drv_load(argv[1], &A, 0, fullsym)) {
+        fprintf(stderr, "Error: failed to load %s\n", argv[1]);
+        return 1;
+    }
+    if (A.m != A.n || A.n < 1) {
+        fprintf(stderr, "Error: the matrix is not square\n");
+        return 1;
+    }
+    const int n = A.n, nnz_s = A.rowptr[A.m];
+    const size_t vsz = fp32 ? sizeof(float) : sizeof(double), msz = m32 ? sizeof(float) : sizeof(double);
+    const rsp_datatype_t dt = fp32 ? RSP_R_32F : RSP_R_64F, mt = m32 ? RSP_R_32F : RSP_R_64F;
+    void *hv = malloc((size_t)(nnz_s ? nnz_s : 1) * vsz);
+    void *hm = malloc((size_t)(nnz_s ? nnz_s : 1) * msz);
+    void *hb = malloc((size_t)n * vsz);
+    double *ones = (double *)malloc((size_t)n * sizeof(double));
+    double *hx = (double *)malloc((size_t)n * sizeof(double));
+    double *hax = (double *)malloc((size_t)n * sizeof(double));
+    for (int i = 0; i < n; i++) ones[i] = 1.0;
+    demote(hv, A.values, (size_t)nnz_s, fp32);
+    demote(hm, A.values, (size_t)nnz_s, m32);
+    demote(hb, ones, (size_t)n, fp32);
+
+    rsp_handle_t handle = NULL;
+    RSP_OR_FAIL(rsp_create(&handle));
+    RSP_OR_FAIL(rsp_set_ftz(handle, ftz));
+
+    int *d_rp = NULL, *d_ci = NULL;
+    void *d_v = NULL, *d_m = NULL, *d_b = NULL, *d_x = NULL;
+    HIP_OR_FAIL(hipMalloc((void **)&d_rp, ((size_t)n + 1) * sizeof(int)));
+    HIP_OR_FAIL(hipMalloc((void **)&d_ci, (size_t)(nnz_s ? nnz_s : 1) * sizeof(int)));
+    HIP_OR_FAIL(hipMalloc(&d_v, (size_t)(nnz_s ? nnz_s : 1) * vsz));
+    HIP_OR_FAIL(hipMalloc(&d_m, (size_t)(nnz_s ? nnz_s : 1) * msz));
+    HIP_OR_FAIL(hipMalloc(&d_b, (size_t)n * vsz));
+    HIP_OR_FAIL(hipMalloc(&d_x, (size_t)n * vsz));
+    HIP_OR_FAIL(hipMemcpy(d_rp, A.rowptr, ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OR_FAIL(hipMemcpy(d_ci, A.colidx, (size_t)nnz_s * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OR_FAIL(hipMemcpy(d_v, hv, (size_t)nnz_s * vsz, hipMemcpyHostToDevice));
+    HIP_OR_FAIL(hipMemcpy(d_m, hm, (size_t)nnz_s * msz, hipMemcpyHostToDevice));
+    HIP_OR_FAIL(hipMemcpy(d_b, hb, (size_t)n * vsz, hipMemcpyHostToDevice));
+    HIP_OR_FAIL(hipMemset(d_x, 0, (size_t)n * vsz));
+
+    rsp_spmat_t mat = NULL;
+    RSP_OR_FAIL(rsp_create_csr(&mat, n, n, A.nnz, d_rp, d_ci, d_v, dt));
+
+    hipEvent_t start, stop;
+    HIP_OR_FAIL(hipEventCreate(&start));
+    HIP_OR_FAIL(hipEventCreate(&stop));
+    float time_symbolic = 0.0f, time_numeric = 0.0f, time_solve = 0.0f;
+
+    rsp_ilu0_info_t info = NULL;
+    if (use_m) {
+        RSP_OR_FAIL(rsp_create_ilu0_info(&info));
+        double t0 = drv_wtime();
+        RSP_OR_FAIL(rsp_ilu0_analysis(handle, n, A.nnz, d_rp, d_ci, info));
+        time_symbolic = (float)((drv_wtime() - t0) * 1e3);
+        int pos = -1;
+        if (rsp_ilu0_zero_pivot(handle, info, &pos) == RSP_STATUS_ZERO_PIVOT) {
+            fprintf(stderr, "Error: A(%d,%d) is missing\n", pos, pos);
+            return 1;
+        }
+        HIP_OR_FAIL(hipEventRecord(start, NULL));
+        RSP_OR_FAIL(rsp_ilu0_factor(handle, info, mt, d_m));
+        HIP_OR_FAIL(hipEventRecord(stop, NULL));
+        HIP_OR_FAIL(hipEventSynchronize(stop));
+        HIP_OR_FAIL(hipEventElapsedTime(&time_numeric, start, stop));
+    }
+
+    rsp_bicgstab_t solver = NULL;
+    RSP_OR_FAIL(rsp_bicgstab_create(handle, mat, info, mt, d_m, &solver));
+    int iters = 0;
+    double relres = 0.0;
+    rsp_solve_reason_t reason = RSP_SOLVE_MAX_ITERS;
+    HIP_OR_FAIL(hipEventRecord(start, NULL));
+    RSP_OR_FAIL(rsp_bicgstab_solve(handle, solver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
+    HIP_OR_FAIL(hipEventRecord(stop, NULL));
+    HIP_OR_FAIL(hipEventSynchronize(stop));
+    HIP_OR_FAIL(hipEventElapsedTime(&time_solve, start, stop));
+
+    /* the true residual, fp64 on the host */
+    void *hxt = malloc((size_t)n * vsz);
+    HIP_OR_FAIL(hipMemcpy(hxt, d_x, (size_t)n * vsz, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) hx[i] = fp32 ? (double)((float *)hxt)[i] : ((double *)hxt)[i];
+    rsp_host_spmv_f64(n, A.rowptr, A.colidx, A.values, hx, hax);
+    double rn = 0.0, bn = 0.0;
+    for (int i = 0; i < n; i++) {
+        const double d = ones[i] - hax[i];
+        rn += d * d;
+        bn += ones[i] * ones[i];
+    }
+
+    printf(fp32 ? "SINGLE PRECISION ITERATION IN  MILLISECONDS\n " : "DOUBLE PRECISION ITERATION IN  MILLISECONDS\n ");
+    printf("Symbolic = %f\n Numeric = %f \n Solve = %f\n Iterations = %d\n Reason = %d\n Relative residual = %e\n",
+           time_symbolic, time_numeric, time_solve, iters, (int)reason, sqrt(rn) / sqrt(bn));
+
+    if (dump && *dump) {
+        FILE *fp = fopen(dump, "wb");
+        if (fp) {
+            fwrite(hxt, vsz, (size_t)n, fp);
+            fclose(fp);
+        }
+    }
+
+    hipEventDestroy(start);
+    hipEventDestroy(stop);
+    rsp_bicgstab_destroy(solver);
+    if (info) rsp_destroy_ilu0_info(info);
+    rsp_destroy_spmat(mat);
+    rsp_destroy(handle);
+    hipFree(d_rp);
+    hipFree(d_ci);
+    hipFree(d_v);
+    hipFree(d_m);
+    hipFree(d_b);
+    hipFree(d_x);
+    free(hv);
+    free(hm);
+    free(hb);
+    free(ones);
+    free(hx);
+    free(hax);
+    free(hxt);
+    rsp_csr_free(&A);
+    return 0;
+}

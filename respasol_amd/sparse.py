@@ -15,6 +15,10 @@ Mapping to the reference's cuSPARSE usage:
   Ilu0.solve_zero_pivot  cusparseXcsrsv2_zeroPivot (the csrsv2 infos, GPU/ilu0.cu:143-150)
   Ilu0.factor            cusparse?csrilu02                   (GPU/ilu0.cu:264-268)
   Ilu0.solve_lower       cusparse?csrsv2_solve, desc_L, op N / op T (GPU/ilu0.cu:296-302)
+  BiCGStab               the loop those calls are normally used in: ILU(0)-
+                         preconditioned BiCGStab (rsp_bicgstab_*; no single
+                         cuSPARSE call)
+  dot                    cublasDdot on the solver's reduction (rsp_dot)
 Errors raise RspError carrying the rsp_status_t (numbered like cusparseStatus_t).
 """
 from __future__ import annotations
@@ -325,6 +329,88 @@ class Ilu0:
             pass
 
 
+class SolveResult:
+    """What BiCGStab.solve returns: x (the solution tensor), iters, relres
+    (recurrence ||r|| / ||b|| at the last check), reason (_lib.SOLVE_*) and
+    history (relres after each checked iteration)."""
+
+    __slots__ = ("x", "iters", "relres", "reason", "history")
+
+    def __init__(self, x, iters, relres, reason, history):
+        self.x, self.iters, self.relres, self.reason, self.history = x, iters, relres, reason, history
+
+    @property
+    def converged(self) -> bool:
+        return self.reason == _lib.SOLVE_CONVERGED
+
+    def __repr__(self) -> str:
+        return (f"SolveResult(iters={self.iters}, relres={self.relres:.3e}, "
+                f"reason={self.reason}, n={self.x.numel()})")
+
+
+class BiCGStab:
+    """Right-preconditioned BiCGStab on A (rsp_bicgstab_*), M = L U from the
+    ILU(0) `factor` values of `ilu` (analysed, factored by the caller), or
+    M = I without `ilu`. A's dtype is the iteration type; factor's dtype (the
+    preconditioner type) must not be wider. A, ilu and factor are kept alive."""
+
+    CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
+
+    def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
+                 factor: torch.Tensor | None = None):
+        if ilu is not None and factor is None:
+            raise ValueError("an ILU(0) preconditioner needs its factored values")
+        if factor is not None and factor.dtype not in _DT:
+            raise TypeError("factor must be float64 or float32")
+        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.dtype = A.dtype
+        self._s = C.c_void_p()
+        check(rsp.rsp_bicgstab_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
+                                      _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
+                                      _ptr(factor) if ilu is not None else None, C.byref(self._s)),
+              "rsp_bicgstab_create")
+
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, rtol: float = 1e-10,
+              max_iters: int = 1000, check_every: int = 1) -> SolveResult:
+        """Solve A x = b from x0 (default 0); x0 is not modified."""
+        if b.dtype != self.dtype or b.numel() != self.A.m:
+            raise ValueError("b has the wrong dtype or length")
+        if x0 is not None and (x0.dtype != self.dtype or x0.numel() != self.A.m):
+            raise ValueError("x0 has the wrong dtype or length")
+        with torch.cuda.stream(self.handle.stream):
+            x = torch.zeros_like(b) if x0 is None else x0.clone()
+        iters, reason, rel = C.c_int(), C.c_int(), C.c_double()
+        check(rsp.rsp_bicgstab_solve(self.handle.ptr, self._s, _ptr(b), _ptr(x), float(rtol),
+                                     int(max_iters), int(check_every), C.byref(iters), C.byref(rel),
+                                     C.byref(reason)), "rsp_bicgstab_solve")
+        count = C.c_int()
+        check(rsp.rsp_bicgstab_history(self._s, 0, None, C.byref(count)), "rsp_bicgstab_history")
+        hist = (C.c_double * max(count.value, 1))()
+        check(rsp.rsp_bicgstab_history(self._s, count.value, hist, C.byref(count)), "rsp_bicgstab_history")
+        return SolveResult(x, iters.value, rel.value, reason.value, list(hist[:count.value]))
+
+    def close(self) -> None:
+        if self._s:
+            rsp.rsp_bicgstab_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dot(handle: Handle, x: torch.Tensor, y: torch.Tensor) -> float:
+    """sum x_i y_i in fp64, in an order fixed by the length (rsp_dot)."""
+    if x.dtype != y.dtype or x.dtype not in _DT or x.numel() != y.numel():
+        raise ValueError("dot: x and y must share dtype (float64 / float32) and length")
+    r = C.c_double()
+    check(rsp.rsp_dot(handle.ptr, _DT[x.dtype], x.numel(), C.c_void_p(x.data_ptr()),
+                      C.c_void_p(y.data_ptr()), C.byref(r)), "rsp_dot")
+    return r.value
+
+
 def gather(handle: Handle, idx: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> None:
     """dst[i] = src[idx[i]] (rsp_gather; idx int64, all on the device)."""
     if idx.dtype != torch.int64 or src.dtype != dst.dtype or dst.numel() < idx.numel():
@@ -341,4 +427,5 @@ def scatter(handle: Handle, idx: torch.Tensor, src: torch.Tensor, dst: torch.Ten
           "rsp_scatter")
 
 
-__all__ = ["Handle", "SpMat", "Ilu0", "upload_csr", "gather", "scatter", "RspError"]
+__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "SolveResult", "dot", "upload_csr", "gather", "scatter",
+           "RspError"]

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""ILU(0)-preconditioned BiCGStab on the moderate surrogates: does a narrower
+preconditioner reach the same residual in less time?
+
+    python scripts/bench_solve.py [--names A,B] [--scale S] [--rtol R] [--maxit N]
+                                  [--out FILE.jsonl]
+
+Per matrix (b = 1, x0 = 0, fp64 iteration) and per configuration
+    fp64      fp64 ILU(0) factor and solves
+    fp32      fp32 factor and solves, the handle without FTZ
+    fp32ftz   fp32 factor and solves, the handle with FTZ
+one JSON line: iterations, reason (0 converged, 1 max iterations, 2
+breakdown), the recurrence residual, the TRUE relative residual (fp64, host),
+solve_ms (event-timed, median of 5 solves after one warm-up), and the cost of
+the same work's library calls stand-alone: spmv_ms (one A x) and apply_ms (one
+L solve + U solve in the preconditioner's type), each the median over 5 event
+-timed loops of 2 * max(iterations, 1) calls. own_ms = solve_ms - iterations *
+(2 spmv_ms + 2 apply_ms) is what the solver adds: its five vector kernels per
+iteration (seven with a narrower preconditioner), the read-back, and the
+launch gaps. A matrix that ends in MAX_ITERS or BREAKDOWN is a result, not a
+failure. A symmetric surrogate is its stored lower triangle (as everywhere in
+this project), so its ILU(0) is exact and one iteration solves it.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from respasol_amd import _lib, csr  # noqa: E402
+from respasol_amd.sparse import BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
+
+CONFIGS = (("fp64", torch.float64, False), ("fp32", torch.float32, False), ("fp32ftz", torch.float32, True))
+
+
+def timed_ms(fn, reps=5):
+    """Median event time of fn() over reps runs (after the caller's warm-up)."""
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out)
+
+
+def true_relres(A, x):
+    ax = np.empty(A.m)
+    xx = np.ascontiguousarray(x, np.float64)
+    _lib.host.rsp_host_spmv_f64(A.m, A.rowptr.ctypes.data_as(_lib.ip), A.colidx.ctypes.data_as(_lib.ip),
+                                A.values.ctypes.data, xx.ctypes.data, ax.ctypes.data)
+    return float(np.linalg.norm(1.0 - ax) / np.sqrt(A.m))
+
+
+def run_one(name, A, cfg, rtol, maxit):
+    label, pdt, ftz = cfg
+    rec = {"matrix": name, "config": label, "n": A.m, "nnz": A.nnz_stored}
+    h = Handle(ftz=ftz)
+    rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
+    mat = SpMat(h, rp, ci, va, A.n)
+    ilu = Ilu0(h, rp, ci)
+    solver = None
+    try:
+        ilu.analysis()
+        fac = va.to(pdt, copy=True)  # the factor overwrites it: never A's own values
+        ilu.factor(fac)
+        try:
+            solver = BiCGStab(h, mat, ilu, fac)
+        except RspError as e:
+            rec["error"] = str(e)
+            return rec
+        b = torch.ones(A.m, dtype=torch.float64, device="cuda")
+        res = solver.solve(b, rtol=rtol, max_iters=maxit)  # warm-up
+        rec.update(iters=res.iters, reason=res.reason, relres=res.relres,
+                   true_relres=true_relres(A, res.x.cpu().numpy()))
+        rec["solve_ms"] = timed_ms(lambda: solver.solve(b, rtol=rtol, max_iters=maxit))
+        calls = 2 * max(res.iters, 1)
+        x = torch.ones(A.m, dtype=torch.float64, device="cuda")
+        y = torch.empty_like(x)
+        spmv = mat.bind(x, y)
+        spmv()
+        rec["spmv_ms"] = timed_ms(lambda: [spmv() for _ in range(calls)]) / calls
+        px = torch.ones(A.m, dtype=pdt, device="cuda")
+        pz, py = torch.empty_like(px), torch.empty_like(px)
+
+        def apply():
+            ilu.solve_lower(fac, px, pz)
+            ilu.solve_upper(fac, pz, py)
+        apply()
+        rec["apply_ms"] = timed_ms(lambda: [apply() for _ in range(calls)]) / calls
+        rec["own_ms"] = rec["solve_ms"] - res.iters * 2 * (rec["spmv_ms"] + rec["apply_ms"])
+        rec["own_share"] = rec["own_ms"] / rec["solve_ms"] if rec["solve_ms"] > 0 else 0.0
+        return rec
+    finally:
+        if solver is not None:
+            solver.close()
+        ilu.close()
+        mat.close()
+        h.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--names", default="", help="comma-separated surrogates (default: the 21 moderate ones)")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--rtol", type=float, default=1e-10)
+    ap.add_argument("--maxit", type=int, default=200)
+    ap.add_argument("--out", default="", help="also append the records to this file")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        sys.exit("bench_solve.py needs an MI355X: there is no CPU fallback")
+    names = [s for s in args.names.split(",") if s] or csr.surrogate_names(0)
+    out = open(args.out, "a") if args.out else None
+    for name in names:
+        A = csr.surrogate(name, args.scale)
+        for cfg in CONFIGS:
+            line = json.dumps(run_one(name, A, cfg, args.rtol, args.maxit))
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()
