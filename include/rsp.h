@@ -294,6 +294,78 @@ rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s);
 rsp_status_t rsp_dot(rsp_handle_t handle, rsp_datatype_t value_type, int64_t n, const void *d_x,
                      const void *d_y, double *result);
 
+/* -------------------------------------- restarted flexible GMRES(m) (FGMRES)
+ *
+ * The second Krylov method on the same operator set: right-preconditioned
+ * flexible GMRES with restart m, M = L U as in rsp_bicgstab_* (or M = I). T is
+ * the iteration type (A's value type), P <= T the preconditioner type.
+ *
+ *   bn = ||b||;  r = b - A x;  beta = ||r||      (each cycle starts from the recomputed residual)
+ *   cycle:  v_0 = r / beta;  g = (beta, 0, ..)
+ *     for j = 0 .. m-1:
+ *         z_j = M^-1 v_j;  w = A z_j
+ *         h  = V_j^T w;  w -= V_j h               (V_j = [v_0 .. v_j]; classical Gram-Schmidt,
+ *         h' = V_j^T w;  w -= V_j h';  h += h'     done twice)
+ *         h_{j+1,j} = ||w||
+ *         the j earlier Givens rotations on column j, rotation j, g rotated;  est = |g_{j+1}| / bn
+ *         if h_{j+1,j} != 0:  v_{j+1} = w / h_{j+1,j}
+ *     R y = g over the k completed columns;  x += Z_k y   (Z = V when M = I)
+ *     r = b - A x;  beta = ||r||;  next cycle unless stopped
+ *
+ * Flexible: z_j is kept, so x += Z y is exact for whatever M^-1 v_j came out
+ * of a narrower preconditioner (plain GMRES forms M^-1 (V y), which is not
+ * sum y_j M^-1 v_j once M^-1 rounds to fp32, and stalls near 1e-7 ||b||).
+ * All dots, norms, the Hessenberg column, the rotations and y are fp64
+ * whatever T; vectors are stored in T. Per iteration: one rsp_spmv, two
+ * triangular solves and four kernels of the solver's own (five with a narrower
+ * preconditioner: the widening of its result); the scalars stay on the device.
+ * Memory: 2 m + 2 vectors of T (m + 2 when M = I) plus the apply's buffers.
+ * Deterministic as rsp_bicgstab_*. */
+#define RSP_GMRES_MAX_RESTART 64
+typedef struct rsp_gmres *rsp_gmres_t;
+/* As rsp_bicgstab_create (same arguments, checks and statuses), with the
+ * restart length: INVALID_VALUE outside [1, RSP_GMRES_MAX_RESTART]. All
+ * vectors are allocated here. */
+rsp_status_t rsp_gmres_create(rsp_handle_t handle, rsp_spmat_t A, rsp_ilu0_info_t info,
+                              rsp_datatype_t precond_type, const void *d_factor, int restart,
+                              rsp_gmres_t *s);
+/* Solves A x = b; arguments, INVALID_VALUE and EXECUTION_FAILED as
+ * rsp_bicgstab_solve. A check is one asynchronous copy into pinned memory and
+ * one event wait, made every check_every iterations (its value: est), at
+ * every cycle end and after the last iteration (its value: the recomputed
+ * ||b - A x|| / ||b||). Stops when est <= rtol at a check (x += Z y follows;
+ * no further residual is computed), or when a cycle's recomputed residual
+ * meets rtol. *relres = the value of the last check; check_every changes no
+ * bit of x for a given iteration count.
+ *   - b = 0, an x0 inside rtol, a non-finite b / x0: as rsp_bicgstab_solve.
+ *   - BREAKDOWN: a non-finite h, or a rotated diagonal that is 0 or not finite
+ *     (A is singular on the Krylov space), detected on the device: x receives
+ *     the update of the completed iterations only, *iters counts those, no NaN
+ *     reaches x. h_{j+1,j} = 0 with a non-zero rotated diagonal is the exact
+ *     solve: it ends the cycle and is no breakdown. */
+rsp_status_t rsp_gmres_solve(rsp_handle_t handle, rsp_gmres_t s, const void *d_b, void *d_x, double rtol,
+                             int max_iters, int check_every, int *iters, double *relres,
+                             rsp_solve_reason_t *reason);
+/* The value of each check of the last solve, as rsp_bicgstab_history. */
+rsp_status_t rsp_gmres_history(rsp_gmres_t s, int cap, double *relres, int *count);
+rsp_status_t rsp_gmres_destroy(rsp_gmres_t s);
+/* One Gram-Schmidt step of the solver on its own, by the solver's three
+ * kernels: d_V holds k columns of n elements, ldv >= n elements apart
+ * (1 <= k <= RSP_GMRES_MAX_RESTART), orthonormal or nearly so; d_w (n
+ * elements) is orthogonalised against them in place, twice. h (HOST, k + 1):
+ * h[0..k) the summed coefficients of both passes, h[k] = ||w|| on return.
+ * Host-blocking; n = 0 gives h = 0. INVALID_VALUE: k outside the range,
+ * ldv < n, n < 0, a NULL pointer. */
+rsp_status_t rsp_orthogonalize(rsp_handle_t handle, rsp_datatype_t value_type, int64_t n, int k,
+                               const void *d_V, int64_t ldv, void *d_w, double *h);
+/* Tests (no device needed): the solver's small least-squares step on HOST
+ * arrays. H: column-major (k + 1) x k upper Hessenberg, columns ldh >= k + 1
+ * apart; minimises ||beta e_1 - H y|| by the solver's Givens rotations and
+ * back-substitution: y (k) and est (k): |g_{j+1}| after column j.
+ * INVALID_VALUE: k outside [1, RSP_GMRES_MAX_RESTART], ldh < k + 1, a NULL
+ * pointer, a non-finite entry or a rotated diagonal that is 0. */
+rsp_status_t rsp_gmres_lsq_host(int k, int ldh, const double *H, double beta, double *y, double *est);
+
 /* ------------------------------------------------ multi-GPU halo exchange */
 
 /* Indexed gather dst[i] = src[idx[i]] for i < n (value_type elements). The

@@ -59,6 +59,7 @@ SOLVE_BREAKDOWN = 2
 # per-workgroup range grows by whole chunks instead).
 KRY_CHUNK = 2048
 KRY_MAX_GRID = 1024
+GMRES_MAX_RESTART = 64  # RSP_GMRES_MAX_RESTART
 
 MM_FULL_SYMMETRIC = 0x1
 MM_QUIET = 0x2
@@ -121,6 +122,13 @@ RSP_PROTOS = {
     "rsp_bicgstab_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),
     "rsp_bicgstab_destroy": (i32, [vp]),
     "rsp_dot": (i32, [vp, i32, i64, vp, vp, C.POINTER(C.c_double)]),
+    "rsp_gmres_create": (i32, [vp, vp, vp, i32, vp, i32, C.POINTER(vp)]),
+    "rsp_gmres_solve": (i32, [vp, vp, vp, vp, C.c_double, i32, i32, ip, C.POINTER(C.c_double), ip]),
+    "rsp_gmres_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),
+    "rsp_gmres_destroy": (i32, [vp]),
+    "rsp_orthogonalize": (i32, [vp, i32, i64, i32, vp, i64, vp, C.POINTER(C.c_double)]),
+    "rsp_gmres_lsq_host": (i32, [i32, i32, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double)]),
     "rsp_gather": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_scatter": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_spmat_set_local_cols": (i32, [vp, i64]),

@@ -1,7 +1,9 @@
 // krylov.hip — the vector side of the ILU(0)-preconditioned BiCGStab iteration
-// (rsp_bicgstab_*) and rsp_dot, for gfx950. The SpMVs and triangular solves of
-// an iteration are the library's existing entry points; everything between
-// them is here, five launches per iteration:
+// (rsp_bicgstab_*), of restarted flexible GMRES (rsp_gmres_*,
+// rsp_orthogonalize: the gm_* kernels, described where they start) and rsp_dot,
+// for gfx950. The SpMVs and triangular solves of an iteration are the library's
+// existing entry points; everything between them is here. BiCGStab, five
+// launches per iteration:
 //
 //   p_update   rho' = (rhat,r); beta = (rho'/rho)(alpha/omega); p = r + beta (p - omega v)
 //   dot_rhv    (rhat,v)
@@ -373,6 +375,360 @@ __global__ __launch_bounds__(kKryThreads) void kry_dot(long long n, long long ch
     put_partial(blk, kKryPartRR, block_sum(acc, lds));
 }
 
+// ---------------------------------------------------------------- GMRES
+//
+// Restarted flexible GMRES (rsp_gmres_*) and rsp_orthogonalize. Column j of a
+// cycle is four launches after the apply and the SpMV that leave w = A z_j:
+//
+//   gm_multidot   partials of (v_i, w), i <= j
+//   gm_update<0>  h = their sums; w -= V h; partials of (v_i, w) again
+//   gm_update<1>  h' = their sums; w -= V h'; partial of (w, w)
+//   gm_normalise  v_{j+1} = w / ||w|| [+ fp32 copy]; workgroup 0: column h + h',
+//                 the rotations, est (rsp::gmres_lsq)
+//
+// and a cycle ends with gm_combine (x += Z y), the SpMV, gm_resid (w = b - A x)
+// and gm_normalise at j = -1 (v_0 = w / ||w||, g = (||w||, 0, ..)).
+//
+// A workgroup walks its range in sub-chunks of kKryChunk elements: thread t
+// keeps its kKryChunk / kKryThreads elements of w in registers (as fp64), so w
+// is read once whatever the number of columns, and the columns pass in batches
+// of kGmBatch accumulators. A batch is reduced over the workgroup as block_sum
+// reduces one value and added to the workgroup's running sums in LDS, one
+// thread per column; with the usual single sub-chunk that is the whole dot.
+// Updates are accumulated in fp64 and rounded once to T; the second dots read
+// the rounded values, i.e. the w that is stored.
+
+constexpr int kGmBatch = 8;
+constexpr int kGmElems = kKryChunk / kKryThreads;  // per thread and sub-chunk
+
+// Flag or stop word set: the same for every thread (see broken()).
+__device__ __forceinline__ bool halted(const double *blk, double *lds) {
+    if (threadIdx.x == 0) lds[0] = (blk[kGmFlag] != 0.0 || blk[kGmStop] != 0.0) ? 1.0 : 0.0;
+    __syncthreads();
+    const bool h = lds[0] != 0.0;
+    __syncthreads();
+    return h;
+}
+
+__device__ __forceinline__ double *gm_part(double *blk, int arr) {
+    return blk + kGmSmall + (size_t)arr * kKryMaxGrid;
+}
+
+// Thread t's groups of sub-chunk [s0, s1): q * kKryThreads + t, q < Q.
+template <typename T>
+struct Sub {
+    static constexpr int V = Grp<T>::V, Q = kGmElems / V;
+    long long j[Q];
+    int cnt[Q];
+    __device__ __forceinline__ Sub(long long s0, long long s1) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            j[q] = s0 + ((long long)q * kKryThreads + threadIdx.x) * V;
+            const long long left = s1 - j[q];
+            cnt[q] = left >= V ? V : (left > 0 ? (int)left : 0);
+        }
+    }
+};
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void sub_load(const T *p, const Sub<T> &sb, double (&d)[kGmElems]) {
+#pragma unroll
+    for (int q = 0; q < Sub<T>::Q; q++) {
+        const Grp<T> g = ld<T, VEC>(p, sb.j[q], sb.cnt[q]);  // (cnt 0: zeros, nothing read)
+#pragma unroll
+        for (int k = 0; k < Sub<T>::V; k++) d[q * Sub<T>::V + k] = (double)g.e[k];
+    }
+}
+
+// d rounded to T and stored; d becomes the stored values
+template <typename T, bool VEC>
+__device__ __forceinline__ void sub_store(T *p, const Sub<T> &sb, double (&d)[kGmElems]) {
+#pragma unroll
+    for (int q = 0; q < Sub<T>::Q; q++) {
+        Grp<T> g;
+#pragma unroll
+        for (int k = 0; k < Sub<T>::V; k++) {
+            g.e[k] = (T)d[q * Sub<T>::V + k];
+            d[q * Sub<T>::V + k] = (double)g.e[k];
+        }
+        st<T, VEC>(p, sb.j[q], sb.cnt[q], g);
+    }
+}
+
+// tot[i] += (v_i, d) over the sub-chunk, i < ncol (elements past the range are
+// zero in both). red: 4 * kGmBatch doubles of LDS.
+template <typename T, bool VEC>
+__device__ __forceinline__ void sub_multidot(const T *V, long long ldv, int ncol, const Sub<T> &sb,
+                                             const double (&d)[kGmElems], double *tot, double *red) {
+    for (int c0 = 0; c0 < ncol; c0 += kGmBatch) {
+        const int nb = ncol - c0 < kGmBatch ? ncol - c0 : kGmBatch;
+        double acc[kGmBatch];
+#pragma unroll
+        for (int b = 0; b < kGmBatch; b++) {
+            acc[b] = 0.0;
+            if (b < nb) {
+                const T *v = V + (long long)(c0 + b) * ldv;
+#pragma unroll
+                for (int q = 0; q < Sub<T>::Q; q++) {
+                    const Grp<T> g = ld<T, VEC>(v, sb.j[q], sb.cnt[q]);
+#pragma unroll
+                    for (int k = 0; k < Sub<T>::V; k++) acc[b] += (double)g.e[k] * d[q * Sub<T>::V + k];
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kGmBatch; b++) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) acc[b] += __shfl_down(acc[b], off, 64);
+            if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * kGmBatch + b] = acc[b];
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < nb)
+            tot[c0 + threadIdx.x] += ((red[threadIdx.x] + red[kGmBatch + threadIdx.x]) +
+                                      red[2 * kGmBatch + threadIdx.x]) + red[3 * kGmBatch + threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// d -= sum_i hs[i] v_i over the sub-chunk, i < ncol, in fp64, i ascending
+template <typename T, bool VEC>
+__device__ __forceinline__ void sub_update(const T *V, long long ldv, int ncol, const Sub<T> &sb,
+                                           double (&d)[kGmElems], const double *hs) {
+#pragma unroll 4
+    for (int i = 0; i < ncol; i++) {
+        const T *v = V + (long long)i * ldv;
+        const double h = hs[i];
+#pragma unroll
+        for (int q = 0; q < Sub<T>::Q; q++) {
+            const Grp<T> g = ld<T, VEC>(v, sb.j[q], sb.cnt[q]);
+#pragma unroll
+            for (int k = 0; k < Sub<T>::V; k++) d[q * Sub<T>::V + k] -= h * (double)g.e[k];
+        }
+    }
+}
+
+// hs[i] = the sum of column i's partials, i < ncol: wave w takes the columns
+// w, w + 4, ..; lane l adds part[l], part[l + 64], .. in that order, then the
+// 64-lane down-tree. The same in every workgroup.
+__device__ __forceinline__ void multi_combine(const double *part0, int ncol, double *hs) {
+    const int lane = threadIdx.x & 63, g = (int)gridDim.x;
+    for (int i = threadIdx.x >> 6; i < ncol; i += kKryThreads / 64) {
+        const double *part = part0 + (size_t)i * kKryMaxGrid;
+        double v = 0.0;
+        for (int p = lane; p < g; p += 64) v += part[p];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) hs[i] = v;
+    }
+    __syncthreads();
+}
+
+#define GM_RANGE(n, chunk)                                        \
+    const long long c0_ = (long long)blockIdx.x * (chunk);        \
+    const long long c1_ = c0_ + (chunk) < (n) ? c0_ + (chunk) : (n)
+#define GM_FOR_SUBS(T)                                                       \
+    for (long long s0_ = c0_; s0_ < c1_; s0_ += kKryChunk)                   \
+        if (const Sub<T> sb(s0_, s0_ + kKryChunk < c1_ ? s0_ + kKryChunk : c1_); true)
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void gm_multidot(long long n, long long chunk, double *blk, int ncol,
+                                                           const T *__restrict__ V, long long ldv,
+                                                           const T *__restrict__ w) {
+    __shared__ double lds[1], tot[kGmLd], red[4 * kGmBatch];
+    if (halted(blk, lds)) return;
+    if ((int)threadIdx.x < ncol) tot[threadIdx.x] = 0.0;
+    __syncthreads();
+    GM_RANGE(n, chunk);
+    GM_FOR_SUBS(T) {
+        double d[kGmElems];
+        sub_load<T, VEC>(w, sb, d);
+        sub_multidot<T, VEC>(V, ldv, ncol, sb, d, tot, red);
+    }
+    if ((int)threadIdx.x < ncol) gm_part(blk, kGmPartD1 + threadIdx.x)[blockIdx.x] = tot[threadIdx.x];
+}
+
+template <typename T, bool VEC, bool SECOND>
+__global__ __launch_bounds__(kKryThreads) void gm_update(long long n, long long chunk, double *blk, int ncol,
+                                                         const T *__restrict__ V, long long ldv,
+                                                         T *__restrict__ w) {
+    __shared__ double lds[kKryThreads / 64], hs[kGmLd], tot[kGmLd], red[4 * kGmBatch];
+    if (halted(blk, lds)) return;
+    multi_combine(gm_part(blk, SECOND ? kGmPartD2 : kGmPartD1), ncol, hs);
+    if ((int)threadIdx.x < ncol) {
+        tot[threadIdx.x] = 0.0;
+        if (blockIdx.x == 0) blk[(SECOND ? kGmH2 : kGmH1) + threadIdx.x] = hs[threadIdx.x];
+    }
+    __syncthreads();
+    double ww = 0.0;
+    GM_RANGE(n, chunk);
+    GM_FOR_SUBS(T) {
+        double d[kGmElems];
+        sub_load<T, VEC>(w, sb, d);
+        sub_update<T, VEC>(V, ldv, ncol, sb, d, hs);
+        sub_store<T, VEC>(w, sb, d);
+        if constexpr (SECOND) {
+#pragma unroll
+            for (int k = 0; k < kGmElems; k++) ww += d[k] * d[k];
+        } else {
+            sub_multidot<T, VEC>(V, ldv, ncol, sb, d, tot, red);
+        }
+    }
+    if constexpr (SECOND) {
+        ww = block_sum(ww, lds);
+        if (threadIdx.x == 0) gm_part(blk, kGmPartNrm)[blockIdx.x] = ww;
+    } else {
+        if ((int)threadIdx.x < ncol) gm_part(blk, kGmPartD2 + threadIdx.x)[blockIdx.x] = tot[threadIdx.x];
+    }
+}
+
+// w = b - w, partials of (w, w) and, if FIRST, of (b, b)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void gm_resid(long long n, long long chunk, double *blk, int first,
+                                                        const T *__restrict__ b, T *__restrict__ w) {
+    __shared__ double lds[kKryThreads / 64];
+    double bb = 0.0, rr = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> gb = ld<T, VEC>(b, j, cnt), gv = ld<T, VEC>(w, j, cnt);
+        Grp<T> gr;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) {
+            gr.e[k] = gb.e[k] - gv.e[k];
+            if (k < cnt) {
+                bb += (double)gb.e[k] * (double)gb.e[k];
+                rr += (double)gr.e[k] * (double)gr.e[k];
+            }
+        }
+        st<T, VEC>(w, j, cnt, gr);
+    }
+    rr = block_sum(rr, lds);
+    if (threadIdx.x == 0) gm_part(blk, kGmPartRR)[blockIdx.x] = rr;
+    if (first) {
+        bb = block_sum(bb, lds);
+        if (threadIdx.x == 0) gm_part(blk, kGmPartBB)[blockIdx.x] = bb;
+    }
+}
+
+__device__ __forceinline__ double gm_combine_one(double *blk, int arr, double *lds) {
+    const double *part = gm_part(blk, arr);
+    const int g = (int)gridDim.x;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < g; i += kKryThreads) v += part[i];
+    return block_sum(v, lds);
+}
+
+template <typename T, bool VEC, bool COPY>
+__global__ __launch_bounds__(kKryThreads) void gm_normalise(long long n, long long chunk, double *blk, int j,
+                                                            int reset, const T *__restrict__ w,
+                                                            T *__restrict__ dst, float *__restrict__ copy32) {
+    __shared__ double lds[kKryThreads / 64], col[kGmLd + 1], scs[kGmMax], ssn[kGmMax], sg[kGmLd + 1];
+    __shared__ int code;
+    if (!reset && halted(blk, lds)) return;
+    const double nrm = sqrt(gm_combine_one(blk, j < 0 ? kGmPartRR : kGmPartNrm, lds));
+    if (j < 0) {
+        // cycle start: g = (||r||, 0, ..); a zero or non-finite ||r|| is the host's to see first
+        const double bn = sqrt(gm_combine_one(blk, kGmPartBB, lds));
+        const bool bad = bad_divisor(nrm);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (reset || bad) {
+                blk[kGmFlag] = bad ? (double)kGmBreakNorm : 0.0;
+                blk[kGmFlagIt] = 0.0;
+            }
+            blk[kGmStop] = 0.0;
+            blk[kGmDone] = 0.0;
+            blk[kGmBeta] = nrm;
+            blk[kGmBn] = bn;
+            blk[kGmG] = nrm;
+        }
+        if (bad) return;
+    } else if (blockIdx.x == 0) {
+        // column j = h + h' with h_{j+1,j} = ||w||: the small step
+        const int t = threadIdx.x;
+        if (t <= j) {
+            col[t] = blk[kGmH1 + t] + blk[kGmH2 + t];
+            scs[t] = blk[kGmCs + t];
+            ssn[t] = blk[kGmSn + t];
+        }
+        if (t == j + 1) col[t] = nrm;
+        if (t == 0) sg[j] = blk[kGmG + j];
+        __syncthreads();
+        if (t == 0) {
+            code = gmres_lsq(col, j, scs, ssn, sg, nullptr, 0, 0, nullptr);
+            if (code) {
+                blk[kGmFlag] = (double)code;
+                blk[kGmFlagIt] = (double)j;
+            } else {
+                blk[kGmG + j] = sg[j];
+                blk[kGmG + j + 1] = sg[j + 1];
+                blk[kGmCs + j] = scs[j];
+                blk[kGmSn + j] = ssn[j];
+                blk[kGmEst + j] = fabs(sg[j + 1]) / blk[kGmBn];
+                blk[kGmDone] = (double)(j + 1);
+                if (nrm == 0.0) blk[kGmStop] = 1.0;
+            }
+        }
+        __syncthreads();
+        if (code == 0 && t <= j) blk[kGmR + (size_t)j * kGmLd + t] = col[t];
+    }
+    if (j >= 0 && bad_divisor(nrm)) return;  // nothing to normalise: the exact solve, or a breakdown
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> g = ld<T, VEC>(w, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) g.e[k] = (T)((double)g.e[k] / nrm);
+        st<T, VEC>(dst, j, cnt, g);
+        if constexpr (COPY) st_copy32<VEC>(copy32, j, cnt, g);
+    }
+}
+
+// x += sum_i y_i z_i over the completed columns (kGmDone), y from R y = g.
+// Runs whatever the flag says: a breakdown at column j leaves the j columns
+// before it to be added. A non-finite y adds nothing.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void gm_combine(long long n, long long chunk, double *blk,
+                                                          const T *__restrict__ Z, long long ldz,
+                                                          T *__restrict__ x) {
+    __shared__ double R[kGmLd * kGmMax], g[kGmLd], y[kGmMax];
+    __shared__ int ok;
+    const int k = (int)blk[kGmDone];
+    if (k <= 0 || k > kGmMax) return;
+    for (int i = threadIdx.x; i < k * kGmLd; i += kKryThreads) R[i] = blk[kGmR + i];
+    if ((int)threadIdx.x < k) g[threadIdx.x] = blk[kGmG + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        gmres_lsq(nullptr, 0, nullptr, nullptr, g, R, kGmLd, k, y);
+        bool fin = true;
+        for (int i = 0; i < k; i++) fin = fin && __builtin_isfinite(y[i]);
+        ok = fin;
+        if (blockIdx.x == 0) {
+            if (fin) {
+                for (int i = 0; i < k; i++) blk[kGmY + i] = y[i];
+            } else if (blk[kGmFlag] == 0.0) {
+                blk[kGmFlag] = (double)kGmBreakY;
+                blk[kGmFlagIt] = 0.0;
+                blk[kGmDone] = 0.0;
+            }
+        }
+    }
+    __syncthreads();
+    if (!ok) return;
+    GM_RANGE(n, chunk);
+    GM_FOR_SUBS(T) {
+        double d[kGmElems];
+        sub_load<T, VEC>(x, sb, d);
+#pragma unroll 4
+        for (int i = 0; i < k; i++) {
+            const T *z = Z + (long long)i * ldz;
+            const double yi = y[i];
+#pragma unroll
+            for (int q = 0; q < Sub<T>::Q; q++) {
+                const Grp<T> gz = ld<T, VEC>(z, sb.j[q], sb.cnt[q]);
+#pragma unroll
+                for (int e = 0; e < Sub<T>::V; e++) d[q * Sub<T>::V + e] += yi * (double)gz.e[e];
+            }
+        }
+        sub_store<T, VEC>(x, sb, d);
+    }
+}
+
 inline bool aligned16(std::initializer_list<const void *> ps) {
     uintptr_t m = 0;
     for (const void *p : ps) m |= (uintptr_t)p;
@@ -430,11 +786,70 @@ hipError_t launch(KryOp op, const KryArgs &a, hipStream_t s) {
         default:
             return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+template <typename T, bool COPY>
+hipError_t gm_launch(GmOp op, const GmArgs &a, hipStream_t s) {
+    const KryGrid kg = kry_grid(a.n);
+    const dim3 grid(kg.grid), block(kKryThreads);
+    const long long n = a.n, ch = kg.chunk;
+    const T *V = (const T *)a.V, *Z = (const T *)a.Z, *b = (const T *)a.b;
+    T *w = (T *)a.w, *x = (T *)a.x;
+    float *c32 = (float *)a.copy32;
+    const int ncol = a.j + 1;
+    // a column base is 16-byte aligned when the first is and the stride is whole groups
+    const bool vstride = (a.ldv * (long long)sizeof(T)) % 16 == 0, zstride = (a.ldz * (long long)sizeof(T)) % 16 == 0;
+    switch (op) {
+        case kGmResid:
+            KRY_LAUNCH(aligned16({b, w}), (gm_resid<T, true>), (gm_resid<T, false>), n, ch, a.blk, a.first, b, w);
+            break;
+        case kGmNormalise: {
+            if (a.j < -1 || a.j >= kGmMax) return hipErrorInvalidValue;
+            T *dst = (T *)a.V + (long long)(a.j + 1) * a.ldv;
+            KRY_LAUNCH(aligned16({w, dst, c32}), (gm_normalise<T, true, COPY>), (gm_normalise<T, false, COPY>), n,
+                       ch, a.blk, a.j, a.first, (const T *)w, dst, c32);
+            break;
+        }
+        case kGmMultiDot:
+            if (ncol < 1 || ncol > kGmLd) return hipErrorInvalidValue;
+            KRY_LAUNCH(vstride && aligned16({V, w}), (gm_multidot<T, true>), (gm_multidot<T, false>), n, ch, a.blk,
+                       ncol, V, a.ldv, (const T *)w);
+            break;
+        case kGmUpdate1:
+            if (ncol < 1 || ncol > kGmLd) return hipErrorInvalidValue;
+            KRY_LAUNCH(vstride && aligned16({V, w}), (gm_update<T, true, false>), (gm_update<T, false, false>), n,
+                       ch, a.blk, ncol, V, a.ldv, w);
+            break;
+        case kGmUpdate2:
+            if (ncol < 1 || ncol > kGmLd) return hipErrorInvalidValue;
+            KRY_LAUNCH(vstride && aligned16({V, w}), (gm_update<T, true, true>), (gm_update<T, false, true>), n, ch,
+                       a.blk, ncol, V, a.ldv, w);
+            break;
+        case kGmCombine:
+            KRY_LAUNCH(zstride && aligned16({Z, x}), (gm_combine<T, true>), (gm_combine<T, false>), n, ch, a.blk, Z,
+                       a.ldz, x);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
 #undef KRY_LAUNCH
     return hipGetLastError();
 }
 
 }  // namespace
+
+hipError_t gmres(GmOp op, int type, const GmArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    switch (type) {
+        case kKryF32: return gm_launch<float, false>(op, a, s);
+        case kKryF64Copy32: return gm_launch<double, true>(op, a, s);
+#ifndef RSP_FTZ_BUILD
+        case kKryF64: return gm_launch<double, false>(op, a, s);
+#endif
+        default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t krylov(KryOp op, int type, const KryArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;

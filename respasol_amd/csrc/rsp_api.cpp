@@ -48,6 +48,10 @@ struct rsp_context {
     // the partials, allocated on first use, freed by rsp_destroy
     double *d_dot;
     double *h_dot;
+    // rsp_orthogonalize: a GMRES block (rsp::kGmBlockDoubles) and its pinned
+    // mirror (h, h' and the norm's partials), as d_dot / h_dot
+    double *d_gm;
+    double *h_gm;
 };
 
 // The SpMV schedule lives in device memory owned by the matrix descriptor
@@ -261,13 +265,15 @@ rsp_status_t rsp_create(rsp_handle_t *handle) {
     c->d_strace = nullptr;
     c->d_dot = nullptr;
     c->h_dot = nullptr;
+    c->d_gm = nullptr;
+    c->h_gm = nullptr;
     *handle = c;
     return RSP_STATUS_SUCCESS;
 }
 
 rsp_status_t rsp_destroy(rsp_handle_t h) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
-    if (h->d_ftrace || h->d_strace || h->d_dot || h->h_dot) {
+    if (h->d_ftrace || h->d_strace || h->d_dot || h->h_dot || h->d_gm || h->h_gm) {
         int cur = 0;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(h->device);
@@ -275,6 +281,8 @@ rsp_status_t rsp_destroy(rsp_handle_t h) {
         if (h->d_strace) (void)hipFree(h->d_strace);
         if (h->d_dot) (void)hipFree(h->d_dot);
         if (h->h_dot) (void)hipHostFree(h->h_dot);
+        if (h->d_gm) (void)hipFree(h->d_gm);
+        if (h->h_gm) (void)hipHostFree(h->h_gm);
         (void)hipSetDevice(cur);
     }
     delete h;
@@ -2670,12 +2678,10 @@ static void bicgstab_free(rsp_bicgstab *s) {
     delete s;
 }
 
-static rsp_status_t rsp_bicgstab_create_impl(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
-                                             rsp_datatype_t precond_type, const void *d_factor,
-                                             rsp_bicgstab_t *out, rsp_bicgstab *&s) {
-    if (!h) return RSP_STATUS_NOT_INITIALIZED;
-    if (!out) return RSP_STATUS_INVALID_VALUE;
-    *out = nullptr;
+// What both solvers' create calls check and finish before they allocate: the
+// arguments, A's schedule, the L and U solve plans, the factor's zero pivot.
+static rsp_status_t krylov_create_checks(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                         rsp_datatype_t precond_type, const void *d_factor) {
     if (!A || A->rows != A->cols || A->rows < 1) return RSP_STATUS_INVALID_VALUE;
     if (info) {
         if (precond_type != RSP_R_64F && precond_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
@@ -2694,6 +2700,17 @@ static rsp_status_t rsp_bicgstab_create_impl(rsp_handle_t h, rsp_spmat_t A, rsp_
         st = rsp_ilu0_zero_pivot(h, info, &pos);  // U divides by its diagonal
         if (st != RSP_STATUS_SUCCESS) return st;
     }
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t rsp_bicgstab_create_impl(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                             rsp_datatype_t precond_type, const void *d_factor,
+                                             rsp_bicgstab_t *out, rsp_bicgstab *&s) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!out) return RSP_STATUS_INVALID_VALUE;
+    *out = nullptr;
+    const rsp_status_t chk = krylov_create_checks(h, A, info, precond_type, d_factor);
+    if (chk != RSP_STATUS_SUCCESS) return chk;
     s = new rsp_bicgstab;
     s->device = h->device;
     s->A = A;
@@ -2909,6 +2926,324 @@ static rsp_status_t rsp_dot_impl(rsp_handle_t h, rsp_datatype_t value_type, int6
     return RSP_STATUS_SUCCESS;
 }
 
+
+/* ------------------------------------------------ FGMRES + orthogonalize */
+
+// One solver: the basis V (m + 1 columns), w, Z (m columns, with M) and the
+// apply's buffers in one allocation, the device block (rsp::kGm*) and the
+// pinned mirror the checks land in.
+struct rsp_gmres {
+    int device = 0;
+    rsp_spmat_t A = nullptr;
+    rsp_ilu0_info_t info = nullptr;  // null: M = I
+    rsp_datatype_t T = RSP_R_64F, P = RSP_R_64F;
+    const void *factor = nullptr;
+    long long n = 0, ld = 0;  // ld: elements between columns of V / Z
+    int m = 0;
+    void *d_arena = nullptr;
+    char *V = nullptr, *Z = nullptr;  // (M = I: Z = V)
+    void *w = nullptr;
+    void *pin = nullptr, *pmid = nullptr, *pout = nullptr;  // as rsp_bicgstab
+    double *d_blk = nullptr;
+    double *h_pin = nullptr;  // kGmHead + 2 kKryMaxGrid doubles
+    hipEvent_t ev = nullptr;
+    std::vector<double> history;
+    bool mixed() const { return info && P != T; }
+};
+
+static void gmres_free(rsp_gmres *s) {
+    if (!s) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(s->device);
+    if (s->d_arena) (void)hipFree(s->d_arena);
+    if (s->h_pin) (void)hipHostFree(s->h_pin);
+    if (s->ev) (void)hipEventDestroy(s->ev);
+    (void)hipSetDevice(cur);
+    delete s;
+}
+
+static rsp_status_t rsp_gmres_create_impl(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
+                                          rsp_datatype_t precond_type, const void *d_factor, int restart,
+                                          rsp_gmres_t *out, rsp_gmres *&s) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!out) return RSP_STATUS_INVALID_VALUE;
+    *out = nullptr;
+    if (restart < 1 || restart > RSP_GMRES_MAX_RESTART) return RSP_STATUS_INVALID_VALUE;
+    const rsp_status_t st = krylov_create_checks(h, A, info, precond_type, d_factor);
+    if (st != RSP_STATUS_SUCCESS) return st;
+    s = new rsp_gmres;
+    s->device = h->device;
+    s->A = A;
+    s->info = info;
+    s->T = A->type;
+    s->P = info ? precond_type : A->type;
+    s->factor = d_factor;
+    s->n = A->rows;
+    s->m = restart;
+    const size_t tb = align256((size_t)s->n * elem_size(s->T)), pb = align256((size_t)s->n * elem_size(s->P));
+    const size_t blk = align256(rsp::kGmBlockDoubles * sizeof(double));
+    s->ld = (long long)(tb / elem_size(s->T));
+    // V (m + 1), w; with M: Z (m) and the apply's vectors (P)
+    const size_t nt = (size_t)s->m + 2 + (info ? s->m : 0), np = !info ? 0 : (s->mixed() ? 3 : 1);
+    RSP_CHECK_HIP(hipMalloc(&s->d_arena, blk + nt * tb + np * pb));
+    char *at = (char *)s->d_arena;
+    s->d_blk = (double *)at;
+    at += blk;
+    s->V = at;
+    at += ((size_t)s->m + 1) * tb;
+    s->w = at;
+    at += tb;
+    s->Z = s->V;
+    if (info) {
+        s->Z = at;
+        at += (size_t)s->m * tb;
+        if (s->mixed()) {
+            s->pin = at;
+            s->pmid = at + pb;
+            s->pout = at + 2 * pb;
+        } else {
+            s->pmid = at;
+        }
+    }
+    RSP_CHECK_HIP(hipHostMalloc((void **)&s->h_pin, (rsp::kGmHead + 2 * (size_t)rsp::kKryMaxGrid) * sizeof(double),
+                                hipHostMallocDefault));
+    RSP_CHECK_HIP(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
+    *out = s;
+    s = nullptr;
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t rsp_gmres_solve_impl(rsp_handle_t h, rsp_gmres_t s, const void *d_b, void *d_x, double rtol,
+                                         int max_iters, int check_every, int *iters, double *relres,
+                                         rsp_solve_reason_t *reason) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!s || !d_b || !d_x || !iters || !relres || !reason) return RSP_STATUS_INVALID_VALUE;
+    if (max_iters < 0 || check_every < 1 || !(rtol >= 0.0)) return RSP_STATUS_INVALID_VALUE;
+    *iters = 0;
+    *relres = 0.0;
+    *reason = RSP_SOLVE_MAX_ITERS;
+    s->history.clear();
+    s->history.reserve((size_t)max_iters / check_every + (size_t)max_iters / s->m + 2);
+    const int type = s->T == RSP_R_32F ? rsp::kKryF32 : (s->mixed() ? rsp::kKryF64Copy32 : rsp::kKryF64);
+    const bool ftz = h->ftz != 0 && type != rsp::kKryF64;
+    const int G = rsp::kry_grid(s->n).grid;
+    const size_t tb = (size_t)s->ld * elem_size(s->T);
+    const double one_d = 1.0, zero_d = 0.0;
+    const float one_f = 1.0f, zero_f = 0.0f;
+    const void *one = s->T == RSP_R_64F ? (const void *)&one_d : (const void *)&one_f;
+    const void *zero = s->T == RSP_R_64F ? (const void *)&zero_d : (const void *)&zero_f;
+    const void *pone = s->P == RSP_R_64F ? (const void *)&one_d : (const void *)&one_f;
+    rsp::GmArgs a{};
+    a.n = s->n;
+    a.blk = s->d_blk;
+    a.b = d_b;
+    a.x = d_x;
+    a.V = s->V;
+    a.ldv = s->ld;
+    a.Z = s->Z;
+    a.ldz = s->ld;
+    a.w = s->w;
+    a.copy32 = s->mixed() ? s->pin : nullptr;
+    auto kern = [&](rsp::GmOp op, int j, int first) {
+        a.j = j;
+        a.first = first;
+        const hipError_t e = ftz ? rsp_k_ftz::gmres(op, type, a, h->stream) : rsp_k::gmres(op, type, a, h->stream);
+        return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+    };
+    auto spmv = [&](const void *x, void *y) {
+        return spmv_run(h, RSP_OPERATION_NON_TRANSPOSE, one, s->A, x, zero, y, s->T, nullptr, 0);
+    };
+    // z_j = M^-1 v_j as bicgstab_apply: v_j (mixed: its fp32 copy, written by
+    // the kernel that made v_j) -> L -> pmid -> U -> z_j (mixed: widened)
+    auto apply = [&](int j) -> rsp_status_t {
+        const void *in = s->mixed() ? s->pin : (const void *)(s->V + (size_t)j * tb);
+        void *z = s->Z + (size_t)j * tb, *res = s->mixed() ? s->pout : z;
+        rsp_status_t st = rsp_trsv_lower_unit_impl(h, RSP_OPERATION_NON_TRANSPOSE, pone, s->info, s->P, s->factor, in,
+                                                   s->pmid, true);
+        if (st != RSP_STATUS_SUCCESS) return st;
+        st = rsp_trsv_upper_impl(h, pone, s->info, s->P, s->factor, s->pmid, res, true);
+        if (st != RSP_STATUS_SUCCESS || !s->mixed()) return st;
+        rsp::KryArgs k{};
+        k.n = s->n;
+        k.blk = s->d_blk;
+        k.b = res;
+        k.copy32 = z;
+        const hipError_t e = ftz ? rsp_k_ftz::krylov(rsp::kKryWiden, rsp::kKryF64Copy32, k, h->stream)
+                                 : rsp_k::krylov(rsp::kKryWiden, rsp::kKryF64Copy32, k, h->stream);
+        return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+    };
+    // a check: the head (scalars + estimates), at a cycle end the (r,r)
+    // partials too; async copies into the pinned mirror, one event
+    double *hp = s->h_pin;
+    auto read_back = [&](bool rr, bool bb) -> rsp_status_t {
+        RSP_CHECK_HIP(hipMemcpyAsync(hp, s->d_blk, rsp::kGmHead * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (rr)
+            RSP_CHECK_HIP(hipMemcpyAsync(hp + rsp::kGmHead, s->d_blk + rsp::kGmSmall + (size_t)rsp::kGmPartRR * rsp::kKryMaxGrid,
+                                         (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (bb)
+            RSP_CHECK_HIP(hipMemcpyAsync(hp + rsp::kGmHead + rsp::kKryMaxGrid,
+                                         s->d_blk + rsp::kGmSmall + (size_t)rsp::kGmPartBB * rsp::kKryMaxGrid,
+                                         (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipEventRecord(s->ev, h->stream));
+        RSP_CHECK_HIP(hipEventSynchronize(s->ev));
+        return RSP_STATUS_SUCCESS;
+    };
+    const int gen0[2] = {s->info ? s->info->solve_gen[RSP_TRSV_L] : 0, s->info ? s->info->solve_gen[RSP_TRSV_U] : 0};
+#define RSP_TRY(call)                                   \
+    do {                                                \
+        const rsp_status_t st_ = (call);                \
+        if (st_ != RSP_STATUS_SUCCESS) return st_;      \
+    } while (0)
+    // w = b - A x0, (b,b), (r,r)
+    RSP_TRY(spmv(d_x, s->w));
+    RSP_TRY(kern(rsp::kGmResid, 0, 1));
+    RSP_TRY(read_back(true, true));
+    const double bb = rsp::kry_combine_host(hp + rsp::kGmHead + rsp::kKryMaxGrid, G);
+    double rr = rsp::kry_combine_host(hp + rsp::kGmHead, G);
+    const double bnorm = sqrt(bb);
+    if (bb == 0.0) {  // x = 0 solves it
+        rsp::KryArgs k{};
+        k.n = s->n;
+        k.x = d_x;
+        const hipError_t e = ftz ? rsp_k_ftz::krylov(rsp::kKryZero, type, k, h->stream)
+                                 : rsp_k::krylov(rsp::kKryZero, type, k, h->stream);
+        if (e != hipSuccess) return RSP_STATUS_EXECUTION_FAILED;
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        *reason = RSP_SOLVE_CONVERGED;
+        return RSP_STATUS_SUCCESS;
+    }
+    if (!std::isfinite(bb) || !std::isfinite(rr)) {  // b or x0 not finite: nothing to iterate on
+        *relres = sqrt(rr) / bnorm;
+        *reason = RSP_SOLVE_BREAKDOWN;
+        return RSP_STATUS_SUCCESS;
+    }
+    double rel = sqrt(rr) / bnorm;
+    int total = 0;
+    bool first = true;
+    if (rel <= rtol) {
+        *reason = RSP_SOLVE_CONVERGED;
+    } else {
+        while (total < max_iters) {
+            // one cycle, from the residual in w
+            RSP_TRY(kern(rsp::kGmNormalise, -1, first ? 1 : 0));
+            first = false;
+            int cols = 0;           // columns launched
+            bool by_est = false;
+            while (cols < s->m && total + cols < max_iters) {
+                const int j = cols;
+                if (s->info) RSP_TRY(apply(j));
+                RSP_TRY(spmv(s->Z + (size_t)j * tb, s->w));
+                RSP_TRY(kern(rsp::kGmMultiDot, j, 0));
+                RSP_TRY(kern(rsp::kGmUpdate1, j, 0));
+                RSP_TRY(kern(rsp::kGmUpdate2, j, 0));
+                RSP_TRY(kern(rsp::kGmNormalise, j, 0));
+                cols++;
+                if (cols == s->m || total + cols == max_iters) break;  // the cycle's end is the check
+                if ((total + cols) % check_every != 0) continue;
+                RSP_TRY(read_back(false, false));
+                if (hp[rsp::kGmFlag] != 0.0 || hp[rsp::kGmStop] != 0.0) break;
+                rel = hp[rsp::kGmEst + j];
+                s->history.push_back(rel);
+                if (rel <= rtol) {
+                    by_est = true;
+                    break;
+                }
+            }
+            // x += Z y over the columns the device completed
+            RSP_TRY(kern(rsp::kGmCombine, cols - 1, 0));
+            if (by_est) {
+                RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+                total += cols;
+                *reason = RSP_SOLVE_CONVERGED;
+                break;
+            }
+            RSP_TRY(spmv(d_x, s->w));
+            RSP_TRY(kern(rsp::kGmResid, 0, 0));
+            RSP_TRY(read_back(true, false));
+            rr = rsp::kry_combine_host(hp + rsp::kGmHead, G);
+            rel = sqrt(rr) / bnorm;
+            const int flag = (int)hp[rsp::kGmFlag];
+            total += (int)hp[rsp::kGmDone];
+            s->history.push_back(rel);
+            if (rel <= rtol) {
+                *reason = RSP_SOLVE_CONVERGED;
+                break;
+            }
+            if (flag || !std::isfinite(rel)) {
+                *reason = RSP_SOLVE_BREAKDOWN;
+                break;
+            }
+        }
+    }
+#undef RSP_TRY
+    *iters = total;
+    *relres = rel;
+    if (s->info && total > 0) {
+        // the L and U solves' give-up words, as rsp_bicgstab_solve
+        int z[5];
+        RSP_CHECK_HIP(hipMemcpyAsync(z, s->info->d_zero, sizeof(z), hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        if (z[2 + RSP_TRSV_L] > gen0[0] || z[2 + RSP_TRSV_U] > gen0[1]) return RSP_STATUS_EXECUTION_FAILED;
+    }
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t rsp_orthogonalize_impl(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, int k,
+                                           const void *d_V, int64_t ldv, void *d_w, double *hh) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (value_type != RSP_R_64F && value_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+    if (!hh || n < 0 || k < 1 || k > RSP_GMRES_MAX_RESTART || ldv < n) return RSP_STATUS_INVALID_VALUE;
+    if (n > 0 && (!d_V || !d_w)) return RSP_STATUS_INVALID_VALUE;
+    for (int i = 0; i <= k; i++) hh[i] = 0.0;
+    if (n == 0) return RSP_STATUS_SUCCESS;
+    const size_t mirror = 2 * (size_t)rsp::kGmLd + rsp::kKryMaxGrid;
+    if (!h->d_gm) {
+        RSP_CHECK_HIP(hipMalloc((void **)&h->d_gm, rsp::kGmBlockDoubles * sizeof(double)));
+        // (flag and stop words clear: the three kernels read them and never set them)
+        RSP_CHECK_HIP(hipMemsetAsync(h->d_gm, 0, rsp::kGmSmall * sizeof(double), h->stream));
+    }
+    if (!h->h_gm) RSP_CHECK_HIP(hipHostMalloc((void **)&h->h_gm, mirror * sizeof(double), hipHostMallocDefault));
+    rsp::GmArgs a{};
+    a.n = n;
+    a.blk = h->d_gm;
+    a.j = k - 1;
+    a.V = const_cast<void *>(d_V);
+    a.ldv = ldv;
+    a.w = d_w;
+    const int type = value_type == RSP_R_64F ? rsp::kKryF64 : rsp::kKryF32;
+    const bool ftz = h->ftz && type == rsp::kKryF32;
+    for (rsp::GmOp op : {rsp::kGmMultiDot, rsp::kGmUpdate1, rsp::kGmUpdate2}) {
+        const hipError_t e = ftz ? rsp_k_ftz::gmres(op, type, a, h->stream) : rsp_k::gmres(op, type, a, h->stream);
+        if (e != hipSuccess) return RSP_STATUS_EXECUTION_FAILED;
+    }
+    const int G = rsp::kry_grid(n).grid;
+    static_assert(rsp::kGmH2 == rsp::kGmH1 + rsp::kGmLd, "h and h' are read back as one range");
+    RSP_CHECK_HIP(hipMemcpyAsync(h->h_gm, h->d_gm + rsp::kGmH1, 2 * (size_t)rsp::kGmLd * sizeof(double),
+                                 hipMemcpyDeviceToHost, h->stream));
+    RSP_CHECK_HIP(hipMemcpyAsync(h->h_gm + 2 * rsp::kGmLd,
+                                 h->d_gm + rsp::kGmSmall + (size_t)rsp::kGmPartNrm * rsp::kKryMaxGrid,
+                                 (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < k; i++) hh[i] = h->h_gm[i] + h->h_gm[rsp::kGmLd + i];
+    hh[k] = sqrt(rsp::kry_combine_host(h->h_gm + 2 * rsp::kGmLd, G));
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t rsp_gmres_lsq_host_impl(int k, int ldh, const double *H, double beta, double *y, double *est) {
+    if (k < 1 || k > RSP_GMRES_MAX_RESTART || ldh < k + 1 || !H || !y || !est) return RSP_STATUS_INVALID_VALUE;
+    std::vector<double> R((size_t)rsp::kGmLd * k), cs(k), sn(k), g(k + 1, 0.0);
+    g[0] = beta;
+    for (int j = 0; j < k; j++) {
+        double *col = R.data() + (size_t)j * rsp::kGmLd;
+        for (int i = 0; i <= j + 1; i++) col[i] = H[i + (size_t)j * ldh];
+        if (rsp::gmres_lsq(col, j, cs.data(), sn.data(), g.data(), nullptr, 0, 0, nullptr)) return RSP_STATUS_INVALID_VALUE;
+        est[j] = fabs(g[j + 1]);
+    }
+    rsp::gmres_lsq(nullptr, 0, nullptr, nullptr, g.data(), R.data(), rsp::kGmLd, k, y);
+    return RSP_STATUS_SUCCESS;
+}
+
 }  // extern "C"
 
 // C-ABI entry points never let a C++ exception out (std::bad_alloc from the
@@ -3038,6 +3373,45 @@ rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s) {
 rsp_status_t rsp_dot(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, const void *d_x, const void *d_y,
                      double *result) {
     return guarded([&] { return rsp_dot_impl(h, value_type, n, d_x, d_y, result); }, [] {});
+}
+
+rsp_status_t rsp_gmres_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
+                              const void *d_factor, int restart, rsp_gmres_t *s) {
+    rsp_gmres *made = nullptr;  // freed here unless create handed it over
+    const rsp_status_t st = guarded([&] { return rsp_gmres_create_impl(h, A, info, precond_type, d_factor, restart, s, made); }, [] {});
+    gmres_free(made);
+    return st;
+}
+
+rsp_status_t rsp_gmres_solve(rsp_handle_t h, rsp_gmres_t s, const void *d_b, void *d_x, double rtol, int max_iters,
+                             int check_every, int *iters, double *relres, rsp_solve_reason_t *reason) {
+    return guarded([&] { return rsp_gmres_solve_impl(h, s, d_b, d_x, rtol, max_iters, check_every, iters, relres, reason); }, [] {});
+}
+
+rsp_status_t rsp_gmres_history(rsp_gmres_t s, int cap, double *relres, int *count) {
+    return guarded([&] {
+        if (!s || !count || cap < 0 || (cap > 0 && !relres)) return RSP_STATUS_INVALID_VALUE;
+        *count = (int)s->history.size();
+        for (int k = 0; k < cap && k < *count; k++) relres[k] = s->history[k];
+        return RSP_STATUS_SUCCESS;
+    }, [] {});
+}
+
+rsp_status_t rsp_gmres_destroy(rsp_gmres_t s) {
+    return guarded([&] {
+        if (!s) return RSP_STATUS_INVALID_VALUE;
+        gmres_free(s);
+        return RSP_STATUS_SUCCESS;
+    }, [] {});
+}
+
+rsp_status_t rsp_orthogonalize(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, int k, const void *d_V,
+                               int64_t ldv, void *d_w, double *hh) {
+    return guarded([&] { return rsp_orthogonalize_impl(h, value_type, n, k, d_V, ldv, d_w, hh); }, [] {});
+}
+
+rsp_status_t rsp_gmres_lsq_host(int k, int ldh, const double *H, double beta, double *y, double *est) {
+    return guarded([&] { return rsp_gmres_lsq_host_impl(k, ldh, H, beta, y, est); }, [] {});
 }
 
 }  // extern "C"

@@ -489,7 +489,7 @@ struct TrsvArgs {
 
 
 // Krylov vector kernels (krylov.hip): the solver's own side of a BiCGStab
-// iteration (rsp_bicgstab_*) and rsp_dot. Every kernel runs kry_grid(n)
+// iteration (rsp_bicgstab_*), of GMRES (rsp_gmres_*, below) and rsp_dot. Every kernel runs kry_grid(n)
 // workgroups of kKryThreads threads; workgroup g owns the contiguous elements
 // [g * chunk, min(n, (g + 1) * chunk)), so the grid and every summation order
 // are functions of n alone. A dot leaves one fp64 partial per workgroup
@@ -565,6 +565,113 @@ inline double kry_combine_host(const double *part, int g) {
     }
     return ((w[0] + w[1]) + w[2]) + w[3];
 }
+
+// Restarted flexible GMRES (krylov.hip gm_* kernels, rsp_gmres_*,
+// rsp_orthogonalize): the same grid, chunks and partials as above. Its device
+// block, all fp64: a head of scalars and the estimates (what a mid-cycle check
+// reads back), the small least-squares problem, then kGmDots partial arrays of
+// kKryMaxGrid entries each.
+constexpr int kGmMax = 64;         // RSP_GMRES_MAX_RESTART
+constexpr int kGmLd = kGmMax + 1;  // leading dimension of R
+enum {
+    kGmStop = 0,    // 1: h_{j+1,j} == 0 with a non-zero rotated diagonal (the exact solve): the cycle's later columns return
+    kGmDone = 1,    // completed columns of the current cycle
+    kGmBeta = 2,    // ||r|| the cycle started from
+    kGmBn = 3,      // ||b||
+    kGmFlag = kKryFlag,      // 0, or kGmBreak*: set once, every later kernel but the combine and the residual
+    kGmFlagIt = kKryFlagIt,  // returns (the slot kKryWiden reads too); the column that set it
+    kGmScalars = 16,
+    kGmEst = kGmScalars,       // kGmMax: |g_{j+1}| / ||b|| after column j
+    kGmHead = kGmEst + kGmMax,
+    kGmR = kGmHead,            // kGmLd x kGmMax, column-major: the rotated Hessenberg matrix (upper triangular)
+    kGmCs = kGmR + kGmLd * kGmMax,
+    kGmSn = kGmCs + kGmMax,
+    kGmG = kGmSn + kGmMax,     // kGmMax + 1
+    kGmY = kGmG + kGmLd,       // kGmMax
+    kGmH1 = kGmY + kGmMax,     // kGmMax + 1: the summed coefficients of the first Gram-Schmidt pass
+    kGmH2 = kGmH1 + kGmLd,     // ... of the second
+    kGmSmall = (kGmH2 + kGmLd + 15) / 16 * 16
+};
+enum {
+    kGmPartRR = 0,
+    kGmPartBB = 1,
+    kGmPartNrm = 2,
+    kGmPartD1 = 3,                // kGmMax + 1 arrays: (v_i, w)
+    kGmPartD2 = kGmPartD1 + kGmLd,  // kGmMax + 1 arrays: (v_i, w) after the first update
+    kGmDots = kGmPartD2 + kGmLd
+};
+enum { kGmBreakH = 1, kGmBreakDiag = 2, kGmBreakNorm = 3, kGmBreakY = 4 };
+constexpr size_t kGmBlockDoubles = kGmSmall + (size_t)kGmDots * kKryMaxGrid;
+enum GmOp {
+    kGmResid,      // w = b - w (w = A x); partials (r,r), and (b,b) if first
+    kGmNormalise,  // j = -1: cycle start, v_0 = w / ||r||, g = (||r||, 0, ..); j >= 0: v_{j+1} = w / ||w||
+                   // [+ fp32 copy], workgroup 0: column j = h + h', rotations, est
+    kGmMultiDot,   // partials D1 of (v_i, w), i <= j
+    kGmUpdate1,    // h from D1; w -= V h; partials D2 of (v_i, w)
+    kGmUpdate2,    // h' from D2; w -= V h'; partial of (w, w)
+    kGmCombine     // y from R y = g over the completed columns; x += Z y
+};
+struct GmArgs {
+    long long n;
+    double *blk;      // kGmBlockDoubles
+    int j;            // the column; kGmNormalise: -1 = cycle start
+    int first;        // kGmResid: (b,b) too; kGmNormalise at j = -1: the block is reset
+    const void *b;    // kGmResid
+    void *x;          // kGmCombine
+    void *V;          // the basis, columns ldv elements apart
+    long long ldv;
+    const void *Z;    // kGmCombine: the preconditioned basis (V when M = I)
+    long long ldz;
+    void *w;
+    void *copy32;     // kKryF64Copy32: the fp32 copy of v_{j+1}
+};
+
+#if defined(__HIPCC__)
+#define RSP_HD __host__ __device__
+#else
+#define RSP_HD
+#endif
+// The small fp64 step of GMRES, shared by the kernels and rsp_gmres_lsq_host.
+// col != null: column j of the Hessenberg matrix (j + 2 entries, h_{j+1,j}
+// last) gets the j earlier rotations (cs, sn), rotation j is formed and stored
+// and applied to g; returns kGmBreakH for a non-finite entry, kGmBreakDiag for
+// a rotated diagonal that is 0 or not finite (nothing is stored then).
+// y != null: back-substitution R y = g over k columns of R (ldr apart).
+RSP_HD inline int gmres_lsq(double *col, int j, double *cs, double *sn, double *g, const double *R, int ldr,
+                            int k, double *y) {
+    if (col) {
+        for (int i = 0; i <= j + 1; i++)
+            if (!(col[i] - col[i] == 0.0)) return kGmBreakH;
+        for (int i = 0; i < j; i++) {
+            const double a = col[i], b = col[i + 1];
+            col[i] = cs[i] * a + sn[i] * b;
+            col[i + 1] = cs[i] * b - sn[i] * a;
+        }
+        const double a = col[j], b = col[j + 1];
+        const double aa = a < 0.0 ? -a : a, ab = b < 0.0 ? -b : b;
+        const double s = aa > ab ? aa : ab;
+        if (s == 0.0) return kGmBreakDiag;
+        const double as = a / s, bs = b / s;
+        const double r = s * sqrt(as * as + bs * bs);
+        if (r == 0.0 || !(r - r == 0.0)) return kGmBreakDiag;
+        const double c = a / r, t = b / r;
+        cs[j] = c;
+        sn[j] = t;
+        col[j] = r;
+        col[j + 1] = 0.0;
+        const double gj = g[j];
+        g[j] = c * gj;
+        g[j + 1] = -(t * gj);
+    }
+    if (y) {
+        for (int i = k - 1; i >= 0; i--) {
+            double v = g[i];
+            for (int l = i + 1; l < k; l++) v -= R[i + (size_t)l * ldr] * y[l];
+            y[i] = v / R[i + (size_t)i * ldr];
+        }
+    }
+    return 0;
+}
 }  // namespace rsp
 
 #define RSP_DECLARE_KERNEL_API(NS)                                                              \
@@ -579,6 +686,7 @@ inline double kry_combine_host(const double *part, int g) {
     void warm_spmv();                                                                           \
     void warm_ilu();                                                                            \
     hipError_t krylov(rsp::KryOp op, int type, const rsp::KryArgs &a, hipStream_t s);           \
+    hipError_t gmres(rsp::GmOp op, int type, const rsp::GmArgs &a, hipStream_t s);              \
     void warm_krylov();                                                                         \
     }
 

@@ -1,18 +1,21 @@
 /*
- * test_solve.c — ILU(0)-preconditioned BiCGStab driver (built as `test_solve`).
+ * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) driver (built as
+ * `test_solve`).
  * No GPU counterpart in the reference; shaped like its direct-solver drivers
  * (Pardiso/test_pardiso.c): b = 1 (:107), solve, relative residual ||b - A x||
  * / ||b|| recomputed on the host (:258-274).
  *
  *   test_solve <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32]
  *              [--precond=fp64|fp32|none] [--ftz] [--rtol=R] [--maxit=N]
- *              [--full-symmetric] [--dump=FILE]
+ *              [--full-symmetric] [--dump=FILE] [--method=bicgstab|gmres]
+ *              [--restart=M]
  *
  * Flow: load as test_ilu0 does (outputbase 0); iteration values in --prec;
  * b = 1, x0 = 0; [timed "Symbolic"] ILU analysis; [timed "Numeric"]
  * factorisation of a copy of the values in the --precond type (default: the
- * --prec type; must not be wider); [timed "Solve"] rsp_bicgstab_solve; the
- * six-line report. Symbolic is wall-clock, Numeric and Solve are event pairs
+ * --prec type; must not be wider); [timed "Solve"] rsp_bicgstab_solve, or with --method=gmres
+ * rsp_gmres_solve of restart length --restart (default 30); the six-line
+ * report. Symbolic is wall-clock, Numeric and Solve are event pairs
  * on the stream. The residual line is the TRUE residual, in fp64 on the host
  * (rsp_host_spmv_f64 on the file's fp64 values), not the recurrence's.
  * Exit 0 for any reason code (converged, max iterations, breakdown);
@@ -61,7 +64,9 @@ int main(int argc, char **argv) {
                 "-- Usage --\n"
                 "  %s <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32] [--precond=fp64|fp32|none]\n"
                 "     [--ftz] [--rtol=R] [--maxit=N] [--full-symmetric] [--dump=FILE]\n"
+                "     [--method=bicgstab|gmres] [--restart=M]\n"
                 "  solves A x = 1 from x0 = 0 by ILU(0)-preconditioned BiCGStab.\n"
+                "  --method=gmres: by restarted flexible GMRES(M) instead (--restart, default 30).\n"
                 "  A symmetric file loads as its lower triangle unless --full-symmetric is given.\n",
                 argv[0]);
         return 2;
@@ -71,6 +76,14 @@ int main(int argc, char **argv) {
     const char *dump = drv_flag(argc, argv, 2, "dump");
     const char *rtol_s = drv_flag(argc, argv, 2, "rtol");
     const char *maxit_s = drv_flag(argc, argv, 2, "maxit");
+    const char *method = drv_flag(argc, argv, 2, "method");
+    const char *restart_s = drv_flag(argc, argv, 2, "restart");
+    const int gmres = method && strcmp(method, "gmres") == 0;
+    const int restart = restart_s && *restart_s ? atoi(restart_s) : 30;
+    if (method && *method && !gmres && strcmp(method, "bicgstab") != 0) {
+        fprintf(stderr, "Error: --method is bicgstab or gmres\n");
+        return 2;
+    }
     const int fp32 = prec && strcmp(prec, "fp32") == 0;
     const int ftz = drv_flag(argc, argv, 2, "ftz") != NULL;
     const int fullsym = drv_flag(argc, argv, 2, "full-symmetric") != NULL;
@@ -152,12 +165,19 @@ int main(int argc, char **argv) {
     }
 
     rsp_bicgstab_t solver = NULL;
-    RSP_OR_FAIL(rsp_bicgstab_create(handle, mat, info, mt, d_m, &solver));
+    rsp_gmres_t gsolver = NULL;
+    if (gmres)
+        RSP_OR_FAIL(rsp_gmres_create(handle, mat, info, mt, d_m, restart, &gsolver));
+    else
+        RSP_OR_FAIL(rsp_bicgstab_create(handle, mat, info, mt, d_m, &solver));
     int iters = 0;
     double relres = 0.0;
     rsp_solve_reason_t reason = RSP_SOLVE_MAX_ITERS;
     HIP_OR_FAIL(hipEventRecord(start, NULL));
-    RSP_OR_FAIL(rsp_bicgstab_solve(handle, solver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
+    if (gmres)
+        RSP_OR_FAIL(rsp_gmres_solve(handle, gsolver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
+    else
+        RSP_OR_FAIL(rsp_bicgstab_solve(handle, solver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
     HIP_OR_FAIL(hipEventRecord(stop, NULL));
     HIP_OR_FAIL(hipEventSynchronize(stop));
     HIP_OR_FAIL(hipEventElapsedTime(&time_solve, start, stop));
@@ -188,7 +208,10 @@ int main(int argc, char **argv) {
 
     hipEventDestroy(start);
     hipEventDestroy(stop);
-    rsp_bicgstab_destroy(solver);
+    if (gmres)
+        rsp_gmres_destroy(gsolver);
+    else
+        rsp_bicgstab_destroy(solver);
     if (info) rsp_destroy_ilu0_info(info);
     rsp_destroy_spmat(mat);
     rsp_destroy(handle);

@@ -18,7 +18,11 @@ Mapping to the reference's cuSPARSE usage:
   BiCGStab               the loop those calls are normally used in: ILU(0)-
                          preconditioned BiCGStab (rsp_bicgstab_*; no single
                          cuSPARSE call)
+  GMRES                  restarted flexible GMRES(m) on the same operators
+                         (rsp_gmres_*)
   dot                    cublasDdot on the solver's reduction (rsp_dot)
+  orthogonalize          one twice-applied Gram-Schmidt step of GMRES
+                         (rsp_orthogonalize)
 Errors raise RspError carrying the rsp_status_t (numbered like cusparseStatus_t).
 """
 from __future__ import annotations
@@ -330,7 +334,7 @@ class Ilu0:
 
 
 class SolveResult:
-    """What BiCGStab.solve returns: x (the solution tensor), iters, relres
+    """What BiCGStab.solve and GMRES.solve return: x (the solution tensor), iters, relres
     (recurrence ||r|| / ||b|| at the last check), reason (_lib.SOLVE_*) and
     history (relres after each checked iteration)."""
 
@@ -401,6 +405,61 @@ class BiCGStab:
             pass
 
 
+class GMRES:
+    """Restarted right-preconditioned flexible GMRES(restart) on A
+    (rsp_gmres_*); the arguments are BiCGStab's, plus the restart length
+    (1 .. _lib.GMRES_MAX_RESTART). Memory: 2 restart + 2 vectors of A's dtype."""
+
+    CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
+
+    def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
+                 factor: torch.Tensor | None = None, restart: int = 30):
+        if ilu is not None and factor is None:
+            raise ValueError("an ILU(0) preconditioner needs its factored values")
+        if factor is not None and factor.dtype not in _DT:
+            raise TypeError("factor must be float64 or float32")
+        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.dtype = A.dtype
+        self.restart = int(restart)
+        self._s = C.c_void_p()
+        check(rsp.rsp_gmres_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
+                                   _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
+                                   _ptr(factor) if ilu is not None else None, self.restart,
+                                   C.byref(self._s)), "rsp_gmres_create")
+
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, rtol: float = 1e-10,
+              max_iters: int = 1000, check_every: int = 1) -> SolveResult:
+        """Solve A x = b from x0 (default 0); x0 is not modified. history
+        holds the value of every check: the estimate inside a cycle, the
+        recomputed ||b - A x|| / ||b|| at a cycle's end."""
+        if b.dtype != self.dtype or b.numel() != self.A.m:
+            raise ValueError("b has the wrong dtype or length")
+        if x0 is not None and (x0.dtype != self.dtype or x0.numel() != self.A.m):
+            raise ValueError("x0 has the wrong dtype or length")
+        with torch.cuda.stream(self.handle.stream):
+            x = torch.zeros_like(b) if x0 is None else x0.clone()
+        iters, reason, rel = C.c_int(), C.c_int(), C.c_double()
+        check(rsp.rsp_gmres_solve(self.handle.ptr, self._s, _ptr(b), _ptr(x), float(rtol), int(max_iters),
+                                  int(check_every), C.byref(iters), C.byref(rel), C.byref(reason)),
+              "rsp_gmres_solve")
+        count = C.c_int()
+        check(rsp.rsp_gmres_history(self._s, 0, None, C.byref(count)), "rsp_gmres_history")
+        hist = (C.c_double * max(count.value, 1))()
+        check(rsp.rsp_gmres_history(self._s, count.value, hist, C.byref(count)), "rsp_gmres_history")
+        return SolveResult(x, iters.value, rel.value, reason.value, list(hist[:count.value]))
+
+    def close(self) -> None:
+        if self._s:
+            rsp.rsp_gmres_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def dot(handle: Handle, x: torch.Tensor, y: torch.Tensor) -> float:
     """sum x_i y_i in fp64, in an order fixed by the length (rsp_dot)."""
     if x.dtype != y.dtype or x.dtype not in _DT or x.numel() != y.numel():
@@ -409,6 +468,24 @@ def dot(handle: Handle, x: torch.Tensor, y: torch.Tensor) -> float:
     check(rsp.rsp_dot(handle.ptr, _DT[x.dtype], x.numel(), C.c_void_p(x.data_ptr()),
                       C.c_void_p(y.data_ptr()), C.byref(r)), "rsp_dot")
     return r.value
+
+
+def orthogonalize(handle: Handle, V: torch.Tensor, w: torch.Tensor) -> np.ndarray:
+    """One Gram-Schmidt step of GMRES, applied twice (rsp_orthogonalize): V is
+    (k, n) with unit-stride rows, the k basis vectors (row stride >= n); w (n)
+    is orthogonalised against them in place. Returns h (k + 1, float64): the
+    summed coefficients and, last, ||w|| afterwards."""
+    if V.dim() != 2 or w.dim() != 1 or V.dtype != w.dtype or V.dtype not in _DT or V.shape[1] != w.numel():
+        raise ValueError("orthogonalize: V must be (k, n) and w (n,), one dtype (float64 / float32)")
+    if V.shape[1] > 1 and V.stride(1) != 1:
+        raise ValueError("orthogonalize: the rows of V must have unit stride")
+    k, n = V.shape
+    ldv = V.stride(0) if k > 1 else max(n, 1)
+    h = np.zeros(k + 1)
+    check(rsp.rsp_orthogonalize(handle.ptr, _DT[V.dtype], n, k, C.c_void_p(V.data_ptr()), ldv,
+                                C.c_void_p(w.data_ptr()), h.ctypes.data_as(C.POINTER(C.c_double))),
+          "rsp_orthogonalize")
+    return h
 
 
 def gather(handle: Handle, idx: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> None:
@@ -427,5 +504,5 @@ def scatter(handle: Handle, idx: torch.Tensor, src: torch.Tensor, dst: torch.Ten
           "rsp_scatter")
 
 
-__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "SolveResult", "dot", "upload_csr", "gather", "scatter",
-           "RspError"]
+__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "GMRES", "SolveResult", "dot", "orthogonalize", "upload_csr",
+           "gather", "scatter", "RspError"]

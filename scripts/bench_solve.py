@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""ILU(0)-preconditioned BiCGStab on the moderate surrogates: does a narrower
-preconditioner reach the same residual in less time?
+"""ILU(0)-preconditioned BiCGStab or GMRES(m) on the moderate surrogates: does a
+narrower preconditioner reach the same residual in less time?
 
     python scripts/bench_solve.py [--names A,B] [--scale S] [--rtol R] [--maxit N]
+                                  [--method bicgstab|gmres] [--restart M]
                                   [--out FILE.jsonl]
 
 Per matrix (b = 1, x0 = 0, fp64 iteration) and per configuration
@@ -17,7 +18,11 @@ L solve + U solve in the preconditioner's type), each the median over 5 event
 -timed loops of 2 * max(iterations, 1) calls. own_ms = solve_ms - iterations *
 (2 spmv_ms + 2 apply_ms) is what the solver adds: its five vector kernels per
 iteration (seven with a narrower preconditioner), the read-back, and the
-launch gaps. A matrix that ends in MAX_ITERS or BREAKDOWN is a result, not a
+launch gaps. With --method gmres (restarted flexible GMRES, restart length
+--restart) an iteration is one SpMV and one apply, so applies = iterations,
+own_ms = solve_ms - iterations * (spmv_ms + apply_ms), and what the solver
+adds is its four kernels per iteration (five with a narrower preconditioner),
+the cycle ends and the read-backs; BiCGStab's applies = 2 iterations. A matrix that ends in MAX_ITERS or BREAKDOWN is a result, not a
 failure. A symmetric surrogate is its stored lower triangle (as everywhere in
 this project), so its ILU(0) is exact and one iteration solves it.
 """
@@ -36,7 +41,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from respasol_amd import _lib, csr  # noqa: E402
-from respasol_amd.sparse import BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
+from respasol_amd.sparse import GMRES, BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
 
 CONFIGS = (("fp64", torch.float64, False), ("fp32", torch.float32, False), ("fp32ftz", torch.float32, True))
 
@@ -62,9 +67,10 @@ def true_relres(A, x):
     return float(np.linalg.norm(1.0 - ax) / np.sqrt(A.m))
 
 
-def run_one(name, A, cfg, rtol, maxit):
+def run_one(name, A, cfg, rtol, maxit, method="bicgstab", restart=30):
     label, pdt, ftz = cfg
-    rec = {"matrix": name, "config": label, "n": A.m, "nnz": A.nnz_stored}
+    rec = {"matrix": name, "config": label, "method": method, "n": A.m, "nnz": A.nnz_stored}
+    per_iter = 1 if method == "gmres" else 2  # SpMVs (and applies) per iteration
     h = Handle(ftz=ftz)
     rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
     mat = SpMat(h, rp, ci, va, A.n)
@@ -75,13 +81,14 @@ def run_one(name, A, cfg, rtol, maxit):
         fac = va.to(pdt, copy=True)  # the factor overwrites it: never A's own values
         ilu.factor(fac)
         try:
-            solver = BiCGStab(h, mat, ilu, fac)
+            solver = (GMRES(h, mat, ilu, fac, restart=restart) if method == "gmres"
+                      else BiCGStab(h, mat, ilu, fac))
         except RspError as e:
             rec["error"] = str(e)
             return rec
         b = torch.ones(A.m, dtype=torch.float64, device="cuda")
         res = solver.solve(b, rtol=rtol, max_iters=maxit)  # warm-up
-        rec.update(iters=res.iters, reason=res.reason, relres=res.relres,
+        rec.update(iters=res.iters, applies=per_iter * res.iters, reason=res.reason, relres=res.relres,
                    true_relres=true_relres(A, res.x.cpu().numpy()))
         rec["solve_ms"] = timed_ms(lambda: solver.solve(b, rtol=rtol, max_iters=maxit))
         calls = 2 * max(res.iters, 1)
@@ -98,7 +105,7 @@ def run_one(name, A, cfg, rtol, maxit):
             ilu.solve_upper(fac, pz, py)
         apply()
         rec["apply_ms"] = timed_ms(lambda: [apply() for _ in range(calls)]) / calls
-        rec["own_ms"] = rec["solve_ms"] - res.iters * 2 * (rec["spmv_ms"] + rec["apply_ms"])
+        rec["own_ms"] = rec["solve_ms"] - res.iters * per_iter * (rec["spmv_ms"] + rec["apply_ms"])
         rec["own_share"] = rec["own_ms"] / rec["solve_ms"] if rec["solve_ms"] > 0 else 0.0
         return rec
     finally:
@@ -115,6 +122,9 @@ def main(argv=None):
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--rtol", type=float, default=1e-10)
     ap.add_argument("--maxit", type=int, default=200)
+    ap.add_argument("--method", choices=("bicgstab", "gmres"), default="bicgstab")
+    ap.add_argument("--restart", type=int, default=30, help="GMRES restart length")
+    ap.add_argument("--configs", default="", help="comma-separated subset of fp64,fp32,fp32ftz")
     ap.add_argument("--out", default="", help="also append the records to this file")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -124,7 +134,9 @@ def main(argv=None):
     for name in names:
         A = csr.surrogate(name, args.scale)
         for cfg in CONFIGS:
-            line = json.dumps(run_one(name, A, cfg, args.rtol, args.maxit))
+            if args.configs and cfg[0] not in args.configs.split(","):
+                continue
+            line = json.dumps(run_one(name, A, cfg, args.rtol, args.maxit, args.method, args.restart))
             print(line, flush=True)
             if out:
                 out.write(line + "\n")
