@@ -2,9 +2,10 @@
 // reference's csrilu02_analysis + 2x csrsv2_analysis, GPU/ilu0.cu:196-252):
 // validation, diagonal positions, level sets of the L / L^T / U DAGs, the
 // symbolic factor (update lists, intra-row stages) and the launch plans of
-// the factor and the solves. Pure host C++ (no HIP calls): rsp_api.cpp
-// downloads the pattern, calls plan_host and uploads the result in one
-// arena; rsp_ilu0_analysis_host runs it on host arrays (tests, profiling).
+// the factor and the solves. Pure host C++ (no HIP calls):
+// api_ilu_analysis.cpp downloads the pattern, calls plan_host and uploads the
+// result in one arena; rsp_ilu0_analysis_host runs it on host arrays (tests,
+// profiling).
 #ifndef RSP_ILU_ANALYSIS_H
 #define RSP_ILU_ANALYSIS_H
 
