@@ -452,12 +452,27 @@ rsp_status_t rsp_ilu0_analysis_host(int n, const int *row_offsets, const int *co
  * column runs) for HOST arrays (base 0, m rows, compute type fp64 / fp32),
  * checked for consistency: every entry of a 16-bit tile decodes to its own
  * column (cbase + offset, or the staged tile's runs at its slot index), every
- * staged tile's runs are ascending and within its slot and run caps. Returns
+ * staged tile's runs are ascending and within its slot and run caps; a packed
+ * tile's slots are read from its record (12-bit fields, padding 0) and its
+ * 16-bit row offsets are checked against row_offsets. Returns
  * the tile count, the entries read through 16-bit values and, of those, the
  * entries of staged tiles; INTERNAL_ERROR if a check fails. */
 rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
                                 rsp_datatype_t compute_type, int64_t *tiles, int64_t *entries_16bit,
                                 int64_t *entries_staged);
+/* Tests and records (no device needed): what ONE call over the schedule of the
+ * same host pattern reads besides the values, x and y, counted per tile on the
+ * vector path. RSP_SPMV_PACK (0, 1, 2 = default; read when a schedule is built) selects
+ * the packed records of staged tiles. stats[0] tiles; [1] packed tiles; [2]
+ * their entries; [3] schedule bytes = 24 per tile (its record, column base and
+ * packed offset) + [6] + the staged tiles' descriptors (8 per run and sentinel,
+ * or 8 + 2 per listed column) + [7]; [4] bytes of the caller's row offsets
+ * still read: 4 (rows + 1) per tile without packed row offsets (4 per long-row
+ * tile); [5] staged tiles; [6] index bytes: 4 per entry of an int32 tile, 2 per
+ * entry of a 16-bit tile, 4 * 256 * NW per packed tile (NW = 3 fp64, 6 fp32);
+ * [7] packed row offsets: 2 (rows + 1) per packed tile, rounded up to 4. */
+rsp_status_t rsp_spmv_plan_stats(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
+                                 rsp_datatype_t compute_type, int64_t stats[8]);
 /* The digest of the plan an rsp_ilu0_analysis built (see above); computed
  * only when the environment sets RSP_ILU_DIGEST=1 at analysis time
  * (INVALID_VALUE otherwise). */

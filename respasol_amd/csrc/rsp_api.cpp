@@ -7,6 +7,7 @@
 // api_krylov.cpp (rsp_internal.h).
 
 #include "rsp_internal.h"
+#include "spmv_pack.h"
 
 #include <atomic>
 
@@ -43,16 +44,18 @@ static SpmvBounds spmv_bounds(int64_t rows, int64_t nnz, int cap) {
 }
 
 // Workspace: [tiles | long rows | chunk partials | per-tile column base |
-// 16-bit column offsets (2 B per stored entry) | staged tiles' runs].
+// per-tile packed-record offset | 16-bit column offsets (2 B per stored
+// entry) | staged tiles' runs, then their packed records].
 struct SpmvLayout {
-    size_t off_long, off_part, off_cbase, off_cidx, off_runs, bytes;
+    size_t off_long, off_part, off_cbase, off_poff, off_cidx, off_runs, bytes;
 };
 static SpmvLayout spmv_layout(const SpmvBounds &b, size_t elem, int64_t nnz, size_t run_ints = 0) {
     SpmvLayout l;
     l.off_long = align256(b.nblocks * sizeof(SpmvBlock));
     l.off_part = l.off_long + align256(b.nlong * sizeof(SpmvLongRow));
     l.off_cbase = l.off_part + align256(b.nslots * 2 * elem);  // value + ticket per slot
-    l.off_cidx = l.off_cbase + align256(b.nblocks * sizeof(int));
+    l.off_poff = l.off_cbase + align256(b.nblocks * sizeof(int));
+    l.off_cidx = l.off_poff + align256(b.nblocks * sizeof(int));
     l.off_runs = l.off_cidx + align256((size_t)std::max<int64_t>(nnz, 0) * sizeof(uint16_t));
     l.bytes = l.off_runs + align256(run_ints * sizeof(int));
     return l;
@@ -148,10 +151,52 @@ struct TilePlan {
     int nslots = 0, nint = 0;
     rsp_an::hvec<int> cbase;
     rsp_an::hvec<uint16_t> c16;
-    rsp_an::hvec<int> runs;  // staged tiles' run descriptors (int pairs), SpmvArgs::runs
-    int64_t nnz_c16 = 0;     // entries read through 16-bit offsets or slot indices
+    rsp_an::hvec<int> runs;  // staged tiles' run descriptors (int pairs), then the packed records; SpmvArgs::runs
+    rsp_an::hvec<int> poff;  // per tile: packed record (SpmvArgs::poffs), -1 = none
+    int64_t nnz_c16 = 0;     // entries not read through the int32 colidx (16-bit offsets, slot indices, packed slots)
     int64_t nnz_staged = 0;  // ... of which in staged tiles
+    int64_t tiles_packed = 0, nnz_packed = 0;  // ... of which in packed tiles
 };
+
+// RSP_SPMV_PACK (plan time): 0 no packed records (the unpacked plan), 1 the
+// slot fields only, 2 (default) slot fields and row offsets. On the big set's
+// batched fp64 launch: 534.8 / 530.7 / 518.8 us (profiles/r07_pack_ab.txt).
+static int spmv_pack_mode() { return std::min(std::max(env_int("RSP_SPMV_PACK", 2), 0), 2); }
+
+// Packed records (spmv_pack.h) of the staged tiles whose slot fields are
+// strictly fewer bytes than their 16-bit words, appended to p.runs after every
+// run descriptor (whose offsets have the smaller range), each 16-B aligned.
+// An offset past the encoding's range leaves the tile unpacked.
+template <typename T>
+static void pack_staged_tiles(const int *rp, TilePlan &p, int mode) {
+    constexpr int VW = SpmvTile<T>::kVec, IT = rsp::kSpmvIter, NTH = rsp::kSpmvThreads;
+    constexpr int IW = rsp_pack::index_words(NTH, IT * VW);
+    p.poff.assign(p.blocks.size(), -1);
+    p.tiles_packed = p.nnz_packed = 0;
+    if (mode <= 0) return;
+    int64_t end = ((int64_t)p.runs.size() + 3) & ~(int64_t)3;
+    for (size_t t = 0; t < p.blocks.size(); t++) {
+        const SpmvBlock &b = p.blocks[t];
+        if (p.cbase[t] > -2 || b.r1 < 0 || !rsp_pack::eligible(NTH, IT * VW, b.k1 - b.k0)) continue;
+        const int64_t words = IW + (mode >= 2 ? rsp_pack::row_words(b.r1 - b.r0) : 0);
+        if (end + words >= (1LL << 30)) break;  // (poff = word << 1 | rows; never reached on real matrices)
+        p.poff[t] = (int)(end << 1) | (mode >= 2 ? 1 : 0);
+        end = (end + words + 3) & ~(int64_t)3;
+        p.tiles_packed++;
+        p.nnz_packed += b.k1 - b.k0;
+    }
+    if (p.tiles_packed == 0) return;
+    p.runs.resize((size_t)end + 4, 0);  // (+ 16 B: a vector load of a record's last words stays inside)
+    rsp_an::parallel_for((long long)p.blocks.size(), 64, [&](long long t0, long long t1) {
+        for (long long t = t0; t < t1; t++) {
+            if (p.poff[(size_t)t] < 0) continue;
+            const SpmvBlock &b = p.blocks[(size_t)t];
+            uint32_t *rec = reinterpret_cast<uint32_t *>(p.runs.data()) + (p.poff[(size_t)t] >> 1);
+            rsp_pack::pack_slots(p.c16.data(), b.k0, b.k1, VW, IT, NTH, rec);
+            if (p.poff[(size_t)t] & 1) rsp_pack::pack_rows(rp, b.r0, b.r1 - b.r0, b.k0 & ~(VW - 1), rec + IW);
+        }
+    });
+}
 
 // spread > 0: a plan of fewer tiles than `spread` (the resident workgroup
 // slots it may use) is re-packed into up to `spread` smaller tiles, so a lone
@@ -248,6 +293,8 @@ static void make_tile_plan(const int *rp, const int *ci, int m, int64_t nnz_boun
     p.cbase.assign(p.blocks.size(), -1);
     p.c16.clear();
     p.runs.clear();
+    p.poff.assign(p.blocks.size(), -1);
+    p.tiles_packed = p.nnz_packed = 0;
     p.nnz_c16 = 0;
     p.nnz_staged = 0;
     if (use_c16 && nnz_s > 0 && nnz_s <= nnz_bound) {
@@ -334,6 +381,10 @@ static void make_tile_plan(const int *rp, const int *ci, int m, int64_t nnz_boun
                 p.cbase[t] = -2 - (int)((off << 8) | nr);
                 p.runs.insert(p.runs.end(), r.begin(), r.end());
             }
+            if (type == RSP_R_64F)
+                pack_staged_tiles<double>(rp, p, spmv_pack_mode());
+            else
+                pack_staged_tiles<float>(rp, p, spmv_pack_mode());
         }
     }
 }
@@ -429,6 +480,8 @@ rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t 
                                      hipMemcpyHostToDevice, h->stream));
         RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_cbase, cbase.data(), cbase.size() * sizeof(int),
                                      hipMemcpyHostToDevice, h->stream));
+        RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_poff, p.poff.data(), p.poff.size() * sizeof(int),
+                                     hipMemcpyHostToDevice, h->stream));
     }
     if (!c16.empty())
         RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_cidx, c16.data(), c16.size() * sizeof(uint16_t),
@@ -457,6 +510,7 @@ rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t 
     mat->off_long = off_long;
     mat->off_part = off_part;
     mat->off_cbase = lay.off_cbase;
+    mat->off_poff = lay.off_poff;
     mat->off_cidx = lay.off_cidx;
     mat->off_runs = lay.off_runs;
     mat->nnz_c16 = nnz_c16;
@@ -488,6 +542,7 @@ rsp_status_t rsp_api::spmv_run(rsp_handle_t h, rsp_operation_t op, const void *a
     a.blocks = (const SpmvBlock *)plan;
     a.nblocks = mat->nblocks;
     a.cbases = (const int *)(plan + mat->off_cbase);
+    a.poffs = (const int *)(plan + mat->off_poff);
     a.cidx = (const unsigned short *)(plan + mat->off_cidx);
     a.runs = (const int *)(plan + mat->off_runs);
     a.cmax = mat->cols > 0 ? (int)(mat->cols - 1) : 0;
@@ -509,6 +564,7 @@ rsp_status_t rsp_api::spmv_run(rsp_handle_t h, rsp_operation_t op, const void *a
         } else {
             a.blocks += mat->nint;
             a.cbases += mat->nint;
+            a.poffs += mat->nint;
             a.nblocks = mat->nblocks - mat->nint;
         }
     }
@@ -580,7 +636,7 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     // layout: per launch [entries | tiles | tile column bases | long rows |
     // 16-bit column offsets of each matrix | long-row partials and tickets of
     // each matrix (zero)], each 16-B aligned
-    struct Span { int first, count; size_t off_e, off_t, off_c, off_l; rsp_an::hvec<size_t> off_16, off_p, off_r; };
+    struct Span { int first, count; size_t off_e, off_t, off_c, off_k, off_l; rsp_an::hvec<size_t> off_16, off_p, off_r; };
     rsp_an::hvec<Span> spans;
     size_t bytes = 0;
     auto tile_range = [part](const TilePlan &p, int *t0, int *t1) {
@@ -588,7 +644,7 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
         *t1 = part == 1 ? p.nint : (int)p.blocks.size();
     };
     for (int first = 0; first < count; first += rsp::kSpmvBatchMax) {
-        Span sp{first, std::min(rsp::kSpmvBatchMax, count - first), 0, 0, 0, 0, {}, {}, {}};
+        Span sp{first, std::min(rsp::kSpmvBatchMax, count - first), 0, 0, 0, 0, 0, {}, {}, {}};
         rsp_an::hvec<rsp_an::hvec<int>> rps((size_t)sp.count), cis((size_t)sp.count);
         int64_t nt_full = 0, nnz_all = 0;
         for (int q = 0; q < sp.count; q++) {
@@ -629,6 +685,8 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
         bytes += (size_t)nt * sizeof(SpmvBlock);
         sp.off_c = bytes;
         bytes += ((size_t)nt * sizeof(int) + 15) & ~(size_t)15;
+        sp.off_k = bytes;
+        bytes += ((size_t)nt * sizeof(int) + 15) & ~(size_t)15;
         sp.off_l = bytes;
         bytes += ((size_t)nl * sizeof(SpmvLongRow) + 15) & ~(size_t)15;
         for (int q = 0; q < sp.count; q++) {
@@ -668,7 +726,7 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
             }
             bool ok = region(sp.off_e, (size_t)sp.count * sizeof(rsp::SpmvBatchEntry)) &&
                       region(sp.off_t, (size_t)nt * sizeof(SpmvBlock)) && region(sp.off_c, (size_t)nt * sizeof(int)) &&
-                      region(sp.off_l, (size_t)nl * sizeof(SpmvLongRow));
+                      region(sp.off_k, (size_t)nt * sizeof(int)) && region(sp.off_l, (size_t)nl * sizeof(SpmvLongRow));
             for (int q = 0; ok && q < sp.count; q++) ok = region(sp.off_16[q], plans[sp.first + q].c16.size() * 2);
             for (int q = 0; ok && q < sp.count; q++) ok = region(sp.off_r[q], plans[sp.first + q].runs.size() * 4);
             for (int q = 0; ok && q < sp.count; q++)
@@ -683,6 +741,7 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
         a.entries = (const rsp::SpmvBatchEntry *)((char *)b->d_mem + sp.off_e);
         a.tiles = (const SpmvBlock *)((char *)b->d_mem + sp.off_t);
         a.cbases = (const int *)((char *)b->d_mem + sp.off_c);
+        a.poffs = (const int *)((char *)b->d_mem + sp.off_k);
         a.longrows = (const SpmvLongRow *)((char *)b->d_mem + sp.off_l);
         a.count = sp.count;
         for (int q = 0; q <= rsp::kSpmvBatchMax; q++)
@@ -717,6 +776,8 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
                        (size_t)(t1 - t0) * sizeof(SpmvBlock));
                 memcpy(host.data() + sp.off_c + (size_t)nt * sizeof(int), p.cbase.data() + t0,
                        (size_t)(t1 - t0) * sizeof(int));
+                memcpy(host.data() + sp.off_k + (size_t)nt * sizeof(int), p.poff.data() + t0,
+                       (size_t)(t1 - t0) * sizeof(int));
             }
             if (nlq > 0)
                 memcpy(host.data() + sp.off_l + (size_t)nl * sizeof(SpmvLongRow), p.longrows.data(),
@@ -743,8 +804,53 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     return RSP_STATUS_SUCCESS;
 }
 
+// A packed record's geometry for `type`: vector width, slot-field words.
+static void pack_geometry(rsp_datatype_t type, int *vw, int *iw) {
+    *vw = type == RSP_R_64F ? SpmvTile<double>::kVec : SpmvTile<float>::kVec;
+    *iw = rsp_pack::index_words(rsp::kSpmvThreads, rsp::kSpmvIter * *vw);
+}
+
+// rsp_spmv_plan_stats: what one call over the schedule of a host pattern
+// reads besides the values, x and y (see include/rsp.h for the rule).
+static rsp_status_t spmv_plan_stats(int m, const int *rp, const int *ci, int64_t nnz, rsp_datatype_t type,
+                                    int64_t *out) {
+    if (m < 0 || (m > 0 && (!rp || !ci)) || !out) return RSP_STATUS_INVALID_VALUE;
+    if (type != RSP_R_64F && type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
+    TilePlan p;
+    make_tile_plan(rp, ci, m, nnz, type, 0, -1, true, p);
+    int vw, iw;
+    pack_geometry(type, &vw, &iw);
+    int64_t staged = 0, idx = 0, desc = 0, rows16 = 0, rowptr = 0;
+    for (size_t t = 0; t < p.blocks.size(); t++) {
+        const SpmvBlock &b = p.blocks[t];
+        const int cb = p.cbase[t], po = p.poff[t];
+        const int64_t len = b.k1 - b.k0, nrows = b.r1 > b.r0 ? b.r1 - b.r0 : 0;
+        idx += po >= 0 ? 4LL * iw : cb == -1 ? 4 * len : 2 * len;
+        if (cb <= -2) {
+            const int code = -2 - cb, nr = code & 255;
+            staged++;
+            desc += nr == 255 ? 8 + 2LL * p.runs[2 * (size_t)(code >> 8) + 1] : 8LL * (nr + 1);
+        }
+        if (po >= 0 && (po & 1))
+            rows16 += 4LL * rsp_pack::row_words((int)nrows);
+        else
+            rowptr += 4 * (nrows + 1);
+    }
+    out[0] = (int64_t)p.blocks.size();
+    out[1] = p.tiles_packed;
+    out[2] = p.nnz_packed;
+    out[3] = 24 * (int64_t)p.blocks.size() + idx + desc + rows16;
+    out[4] = rowptr;
+    out[5] = staged;
+    out[6] = idx;
+    out[7] = rows16;
+    return RSP_STATUS_SUCCESS;
+}
+
 // rsp_spmv_plan_host: the schedule of a host pattern, every 16-bit / staged
-// column decoded back and compared with the pattern.
+// column decoded back and compared with the pattern; a packed tile's slots
+// are read from its record's fields, whose padding must be 0, and its packed
+// row offsets are compared with the row offsets.
 static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t nnz, rsp_datatype_t type,
                                    int64_t *tiles, int64_t *e16, int64_t *est) {
     if (m < 0 || (m > 0 && (!rp || !ci)) || !tiles || !e16 || !est) return RSP_STATUS_INVALID_VALUE;
@@ -752,9 +858,40 @@ static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t 
     TilePlan p;
     make_tile_plan(rp, ci, m, nnz, type, 0, -1, true, p);
     const int ucap = type == RSP_R_64F ? SpmvTile<double>::kStageSlots : SpmvTile<float>::kStageSlots;
+    int vw, iw;
+    pack_geometry(type, &vw, &iw);
+    const int pack_mode = spmv_pack_mode();
+    if (p.poff.size() != p.blocks.size()) return RSP_STATUS_INTERNAL_ERROR;
+    int64_t npk = 0, epk = 0;
     for (size_t t = 0; t < p.blocks.size(); t++) {
         const SpmvBlock &b = p.blocks[t];
-        const int cb = p.cbase[t];
+        const int cb = p.cbase[t], po = p.poff[t];
+        const uint32_t *rec = nullptr;
+        if (po >= 0) {  // the record: a staged, eligible tile; inside `runs`, after the descriptors
+            const int nrows = b.r1 - b.r0, kb = b.k0 & ~(vw - 1);
+            const size_t w0 = (size_t)(po >> 1), words = (size_t)iw + ((po & 1) ? rsp_pack::row_words(nrows) : 0);
+            if (cb > -2 || b.r1 < 0 || pack_mode == 0 || (po & 1) != (pack_mode >= 2) ||
+                !rsp_pack::eligible(rsp::kSpmvThreads, rsp::kSpmvIter * vw, b.k1 - b.k0) || (w0 & 3) ||
+                w0 + words > p.runs.size())
+                return RSP_STATUS_INTERNAL_ERROR;
+            rec = reinterpret_cast<const uint32_t *>(p.runs.data()) + w0;
+            const int nwt = iw / rsp::kSpmvThreads;
+            for (int tid = 0; tid < rsp::kSpmvThreads; tid++)  // fields outside [k0, k1) are 0
+                for (int f = 0; f < rsp::kSpmvIter * vw; f++) {
+                    const long long e = (long long)kb + (long long)((f / vw) * rsp::kSpmvThreads + tid) * vw + f % vw;
+                    if ((e < b.k0 || e >= b.k1) && rsp_pack::get_field(rec + (size_t)tid * nwt, f) != 0)
+                        return RSP_STATUS_INTERNAL_ERROR;
+                }
+            if (po & 1)
+                for (int i = 0; i <= nrows; i++)
+                    if (rsp_pack::unpack_row(rec + iw, i) + kb != rp[b.r0 + i]) return RSP_STATUS_INTERNAL_ERROR;
+            npk++;
+            epk += b.k1 - b.k0;
+        }
+        auto slot_of = [&](int k) {
+            return rec ? (int)rsp_pack::unpack_slot(rec, b.k0, k, vw, rsp::kSpmvIter, rsp::kSpmvThreads)
+                       : (int)p.c16[(size_t)k];
+        };
         if (cb == -1) continue;
         for (int k = b.k0; k < b.k1; k++) {
             int col;
@@ -772,7 +909,7 @@ static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t 
                     const uint16_t *o = reinterpret_cast<const uint16_t *>(r + 2);
                     for (int u = 1; u < U; u++)
                         if (o[u] <= o[u - 1]) return RSP_STATUS_INTERNAL_ERROR;
-                    const int u = p.c16[(size_t)k];
+                    const int u = slot_of(k);
                     if (u >= U) return RSP_STATUS_INTERNAL_ERROR;
                     if (r[0] + o[u] != ci[k]) return RSP_STATUS_INTERNAL_ERROR;
                     continue;
@@ -785,7 +922,7 @@ static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t 
                 for (int j = 1; j <= nr; j++)
                     if (r[2 * j + 1] <= r[2 * j - 1] || (j < nr && r[2 * j] <= r[2 * j - 2] + (r[2 * j + 1] - r[2 * j - 1]) - 1))
                         return RSP_STATUS_INTERNAL_ERROR;
-                const int u = p.c16[(size_t)k];
+                const int u = slot_of(k);
                 if (u >= U) return RSP_STATUS_INTERNAL_ERROR;
                 int j = 0;
                 while (j + 1 < nr && r[2 * (j + 1) + 1] <= u) j++;
@@ -794,6 +931,7 @@ static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t 
             if (col != ci[k]) return RSP_STATUS_INTERNAL_ERROR;
         }
     }
+    if (npk != p.tiles_packed || epk != p.nnz_packed) return RSP_STATUS_INTERNAL_ERROR;
     *tiles = (int64_t)p.blocks.size();
     *e16 = p.nnz_c16;
     *est = p.nnz_staged;
@@ -1092,6 +1230,11 @@ rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_in
     return guarded([&] {
         return spmv_plan_host(m, row_offsets, col_ind, nnz, compute_type, tiles, entries_16bit, entries_staged);
     });
+}
+
+rsp_status_t rsp_spmv_plan_stats(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
+                                 rsp_datatype_t compute_type, int64_t stats[8]) {
+    return guarded([&] { return spmv_plan_stats(m, row_offsets, col_ind, nnz, compute_type, stats); });
 }
 
 }  // the C ABI

@@ -67,7 +67,7 @@ struct rsp_spmat {
     int nblocks, nlong, nslots;
     int nnz_s;                  // rowptr[rows] seen by the planner
     size_t off_long, off_part;  // byte offsets inside d_plan
-    size_t off_cbase, off_cidx, off_runs;
+    size_t off_cbase, off_poff, off_cidx, off_runs;
     int64_t nnz_c16;            // entries read through 16-bit column offsets or slot indices
     int64_t nnz_staged;         // ... of which in staged tiles (x staged in LDS)
     int64_t local_cols;         // rsp_spmat_set_local_cols (-1: not split)

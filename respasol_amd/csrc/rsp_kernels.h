@@ -89,6 +89,11 @@ struct SpmvArgs {
     const int *cbases;
     const unsigned short *cidx;   // 16-bit column offsets / slot indices (tiles with cbases != -1)
     const int *runs;              // staged tiles: {first column, first slot} per run, {0, slots} last
+    // per tile, parallel to cbases: -1, or a staged tile's PACKED record
+    // (spmv_pack.h: 12-bit slot fields, then 16-bit row offsets) at word
+    // runs[poff >> 1]; bit 0: the record carries the row offsets. A packed
+    // tile on the vector path reads neither its cidx words nor (bit 0) rowptr.
+    const int *poffs;
     int cmax;                     // n - 1 (clamp for neighbour entries of partial vectors)
     const SpmvLongRow *longrows;
     int nlong;
@@ -129,6 +134,7 @@ struct SpmvBatchArgs {
     const SpmvBatchEntry *entries;
     const SpmvBlock *tiles;
     const int *cbases;  // per tile, parallel to `tiles`
+    const int *poffs;   // per tile: packed record (SpmvArgs::poffs), relative to the entry's runs
     const SpmvLongRow *longrows;
     int count;
     SpmvBatchTable tiles_at, longs_at;

@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "rsp_kernels.h"
+#include "spmv_pack.h"
 
 #ifndef RSP_KNS
 #define RSP_KNS rsp_k
@@ -184,9 +185,22 @@ __device__ __forceinline__ void lds_barrier() {
 // neighbour entries carry another tile's indices; their products are never
 // read), and after a barrier the products overwrite the image as usual.
 // Same products, same order: the same bits as the gathered tile.
-template <typename T, bool NT, int NTH = kSpmvThreads,
+// PACKED tiles (PK; spmv_pack.h): the slot indices
+// are 12-bit fields of the tile's own record, NW words per thread (one 12-byte
+// load for fp64, 16 + 8 bytes for fp32) instead of IT 16-bit vectors from
+// cidx: 1.5 B per slot of the image instead of 2 B per entry. The words are
+// loaded ahead of the values like the 16-bit vectors and decoded after the
+// loads' burst; fields of slots outside [k0, k1) are 0. PKM 1 / 0: the packed
+// / unpacked form as an instantiation of its own, chosen by the caller's
+// workgroup-uniform branch (fp64), so neither form's loads meet the other's
+// registers at a join — which makes hipcc drain vmcnt in front of the later
+// form's loads, 5 % of the big set's launch. PKM 2: one instantiation that
+// tests pk (fp32, where two cost 73 VGPRs and a wave per SIMD; its unpacked
+// staged tiles are the few short ones).
+template <typename T, bool NT, int PKM, int NTH = kSpmvThreads,
           int IT = SpmvTile<T>::kSlots / (kSpmvThreads * (16 / sizeof(T)))>
-__device__ __forceinline__ void stream_products_staged(const unsigned short *__restrict__ cidx, int2 rd,
+__device__ __forceinline__ void stream_products_staged(const unsigned short *__restrict__ cidx,
+                                                       const unsigned int *__restrict__ pk, int2 rd,
                                                        int nr, const int (&lsl)[SpmvTile<T>::kStageSlots / NTH],
                                                        const T *__restrict__ vals,
                                                        const T *__restrict__ x, int kb, int k1,
@@ -194,15 +208,28 @@ __device__ __forceinline__ void stream_products_staged(const unsigned short *__r
     constexpr int VW = 16 / sizeof(T);
     constexpr int SMAX = SpmvTile<T>::kStageSlots / NTH;
     typedef typename VecT<T, VW>::V V;
-    typedef typename VecT<T, VW>::H H;
     const int tid = threadIdx.x;
     const int last = (k1 - 1) & ~(VW - 1);
-    H ch[IT];
+    // the tile's index words: IT 16-bit vectors (two slots per word), or the
+    // NW words of the packed record — one register array for both forms
+    constexpr int NW = rsp_pack::words_per_thread(IT * VW);
+    constexpr int HW = VW / 2;  // words per 16-bit vector
+    static_assert(NW <= IT * HW, "the packed words fit the unpacked ones' registers");
+    const bool pkd = PKM == 2 ? pk != nullptr : PKM == 1;
+    unsigned int iw[PKM == 1 ? NW : IT * HW];
     V vv[IT];
+    if (pkd) {
+        const unsigned int *w = pk + tid * NW;
 #pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const int e = min(kb + (it * NTH + tid) * VW, last);
-        ch[it] = ld<NT>(reinterpret_cast<const H *>(cidx + e));
+        for (int q = 0; q < NW; ++q) iw[q] = ld<NT>(w + q);
+    } else {
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int e = min(kb + (it * NTH + tid) * VW, last);
+            const unsigned int *w = reinterpret_cast<const unsigned int *>(cidx + e);
+#pragma unroll
+            for (int q = 0; q < HW; ++q) iw[it * HW + q] = ld<NT>(w + q);
+        }
     }
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -257,10 +284,18 @@ __device__ __forceinline__ void stream_products_staged(const unsigned short *__r
         if (k * NTH < U && k * NTH + tid < U) lds[k * NTH + tid] = xs[k];
     lds_barrier();
     T xv[IT][VW];
+    if (pkd) {
 #pragma unroll
-    for (int it = 0; it < IT; ++it)
+        for (int it = 0; it < IT; ++it)
 #pragma unroll
-        for (int j = 0; j < VW; ++j) xv[it][j] = lds[min((int)ch[it][j], U - 1)];
+            for (int j = 0; j < VW; ++j) xv[it][j] = lds[min((int)rsp_pack::get_field(iw, it * VW + j), U - 1)];
+    } else {
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+#pragma unroll
+            for (int j = 0; j < VW; ++j)
+                xv[it][j] = lds[min((int)((iw[(it * VW + j) >> 1] >> (16 * (j & 1))) & 0xffffu), U - 1)];
+    }
     lds_barrier();  // every x read before the products overwrite the image
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -477,12 +512,15 @@ __device__ __forceinline__ void longrow_arrive(const SpmvBlock blk, const int *_
 template <typename T, bool NT, bool BETA>
 __device__ __forceinline__ void spmv_tile(
     const SpmvBlock blk, const int *__restrict__ rowptr, const int *__restrict__ colidx,
-    const unsigned short *__restrict__ cidx, const int *__restrict__ runs, int cbase, int cmax,
+    const unsigned short *__restrict__ cidx, const int *__restrict__ runs, int cbase, int poff, int cmax,
     const T *__restrict__ vals, const T *__restrict__ x, T *__restrict__ y,
     T *partials, T alpha, T beta, int beta_nonzero, int nnz, int vector_ok, T *lds,
     T *wsum, unsigned short *rp_lds, int *hl, int fuse) {
     constexpr int VW = 16 / sizeof(T);
     constexpr int RPQ = (SpmvTile<T>::kMaxRows + kSpmvThreads) / kSpmvThreads;
+    // packed row offsets: two per word
+    constexpr int RPW = (SpmvTile<T>::kMaxRows / 2 + kSpmvThreads) / kSpmvThreads;
+    static_assert(RPW <= RPQ, "the packed row words fit the row offsets' registers");
     const int tid = threadIdx.x;
     const int k0 = blk.k0, k1 = blk.k1;
     // a staged tile's run descriptors: the first load of the tile, so the x
@@ -509,13 +547,26 @@ __device__ __forceinline__ void spmv_tile(
     // after it, so the reduce never waits on global memory
     const int nrows = blk.r1 - blk.r0;
     const int nrows_ld = nrows > 0 ? nrows : 0;  // long-row chunks: r1 < 0
-    int rpv[RPQ];
-#pragma unroll
-    for (int q = 0; q < RPQ; ++q)  // unpredicated (clamped) so nothing waits here
-        rpv[q] = rowptr[blk.r0 + min(tid + q * kSpmvThreads, nrows_ld)];
     // vectors may be used unless the tile reaches the last, partial vector
     const bool vec = vector_ok && k1 > k0 && k1 <= (nnz & ~(VW - 1));
     const int kb = vec ? (k0 & ~(VW - 1)) : k0;
+    // a packed staged tile (workgroup-uniform): its record holds the slot
+    // fields and (bit 0 of poff) the row offsets relative to the vector path's
+    // kb, so only that path reads it; the scalar path keeps cidx / rowptr
+    const unsigned int *rec =
+        vec && staged && poff >= 0 ? reinterpret_cast<const unsigned int *>(runs) + (poff >> 1) : nullptr;
+    const bool prow = rec && (poff & 1);
+    const int nrw = (nrows_ld + 2) >> 1;  // packed row words
+    // one branch-free sequence for both sources (the record's words, or
+    // rowptr): only the base and the clamp differ, so nothing waits here
+    const int *rsrc = prow ? reinterpret_cast<const int *>(rec) +
+                                 kSpmvThreads * rsp_pack::words_per_thread(SpmvTile<T>::kSlots / kSpmvThreads)
+                           : rowptr + blk.r0;
+    const int rlim = prow ? nrw - 1 : nrows_ld;
+    int rpv[RPQ];
+#pragma unroll
+    for (int q = 0; q < RPQ; ++q)  // unpredicated (clamped)
+        rpv[q] = rsrc[min(tid + q * kSpmvThreads, rlim)];
 #ifdef RSP_SPMV_PROBE_LOADS  // diagnostic builds only (make probe; scripts/spmv_probe.py loadsonly)
     if (vec) {
         probe_tile_loads<T, NT>(colidx, vals, y, blk, kb, k1, rpv[0]);
@@ -524,16 +575,28 @@ __device__ __forceinline__ void spmv_tile(
 #endif
     if (vec && cbase >= 0)
         stream_products<T, NT, true>(colidx, cidx, cbase, cmax, vals, x, kb, k1, lds);
+    else if (vec && staged && sizeof(T) == 4)
+        stream_products_staged<T, NT, 2>(cidx, rec, rd, nr, lsl, vals, x, kb, k1, lds);
+    else if (vec && rec)
+        stream_products_staged<T, NT, 1>(cidx, rec, rd, nr, lsl, vals, x, kb, k1, lds);
     else if (vec && staged)
-        stream_products_staged<T, NT>(cidx, rd, nr, lsl, vals, x, kb, k1, lds);
+        stream_products_staged<T, NT, 0>(cidx, rec, rd, nr, lsl, vals, x, kb, k1, lds);
     else if (vec)
         stream_products<T, NT>(colidx, cidx, 0, 0, vals, x, kb, k1, lds);
     else
         stream_products_scalar<T>(colidx, vals, x, k0, kb, k1, lds);
+    if (prow) {  // already relative to kb, two per word
 #pragma unroll
-    for (int q = 0; q < RPQ; ++q) {
-        const int i = tid + q * kSpmvThreads;
-        if (i <= nrows) rp_lds[i] = (unsigned short)(rpv[q] - kb);  // < kSlots + kVec
+        for (int q = 0; q < RPW; ++q) {
+            const int i = tid + q * kSpmvThreads;
+            if (i < nrw) reinterpret_cast<unsigned int *>(rp_lds)[i] = (unsigned int)rpv[q];
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < RPQ; ++q) {
+            const int i = tid + q * kSpmvThreads;
+            if (i <= nrows) rp_lds[i] = (unsigned short)(rpv[q] - kb);  // < kSlots + kVec
+        }
     }
     if (tid == 0) hl[0] = 0;  // the tile's heavy-row count (reduce_tile_rows)
     lds_barrier();
@@ -577,14 +640,15 @@ template <typename T, bool NT, bool BETA>
 __global__ __launch_bounds__(kSpmvThreads) void spmv_tiles(
     const int *__restrict__ rowptr, const int *__restrict__ colidx, const T *__restrict__ vals,
     const T *__restrict__ x, T *__restrict__ y, const SpmvBlock *__restrict__ blocks, int nblocks,
-    const int *__restrict__ cbases, const unsigned short *__restrict__ cidx, const int *__restrict__ runs,
-    int cmax, T *partials, T alpha, T beta, int beta_nonzero, int nnz, int vector_ok, int fuse) {
+    const int *__restrict__ cbases, const int *__restrict__ poffs, const unsigned short *__restrict__ cidx,
+    const int *__restrict__ runs, int cmax, T *partials, T alpha, T beta, int beta_nonzero, int nnz,
+    int vector_ok, int fuse) {
     __shared__ __attribute__((aligned(16))) T lds[SpmvTile<T>::kSlots];
     __shared__ T wsum[kSpmvThreads / 64];
     __shared__ int hl[1 + kSpmvHeavyMax];  // heavy rows of the tile: count, list
-    __shared__ unsigned short rp_lds[SpmvTile<T>::kMaxRows + 2];  // row offsets - kb
+    __shared__ __attribute__((aligned(4))) unsigned short rp_lds[SpmvTile<T>::kMaxRows + 2];  // row offsets - kb
     const int b = xcd_swizzle(blockIdx.x, nblocks);
-    spmv_tile<T, NT, BETA>(blocks[b], rowptr, colidx, cidx, runs, cbases[b], cmax, vals, x, y,
+    spmv_tile<T, NT, BETA>(blocks[b], rowptr, colidx, cidx, runs, cbases[b], poffs[b], cmax, vals, x, y,
                            partials, alpha, beta, beta_nonzero, nnz, vector_ok, lds, wsum, rp_lds, hl,
                            fuse);
 }
@@ -630,11 +694,12 @@ __global__ __launch_bounds__(64) void spmv_longrow_fixup(const SpmvLongRow *__re
 template <typename T, bool NT, bool BETA, bool SWZ>
 __global__ __launch_bounds__(kSpmvThreads) void spmv_tiles_batch(
     const SpmvBatchEntry *__restrict__ entries, const SpmvBlock *__restrict__ tiles,
-    const int *__restrict__ cbases, SpmvBatchTable at, T alpha, T beta, int fuse) {
+    const int *__restrict__ cbases, const int *__restrict__ poffs, SpmvBatchTable at, T alpha, T beta,
+    int fuse) {
     __shared__ __attribute__((aligned(16))) T lds[SpmvTile<T>::kSlots];
     __shared__ T wsum[kSpmvThreads / 64];
     __shared__ int hl[1 + kSpmvHeavyMax];  // heavy rows of the tile: count, list
-    __shared__ unsigned short rp_lds[SpmvTile<T>::kMaxRows + 2];  // row offsets - kb
+    __shared__ __attribute__((aligned(4))) unsigned short rp_lds[SpmvTile<T>::kMaxRows + 2];  // row offsets - kb
     const int b = blockIdx.x;
     // lo / hi selected inside the compare chain on the kernel arguments
     // (preloaded into SGPRs, so no memory latency in front of the tile
@@ -653,7 +718,7 @@ __global__ __launch_bounds__(kSpmvThreads) void spmv_tiles_batch(
         }
     const int t = lo + (SWZ ? xcd_swizzle(b - lo, hi - lo) : b - lo);
     const SpmvBatchEntry e = entries[j];
-    spmv_tile<T, NT, BETA>(tiles[t], e.rowptr, e.colidx, e.cidx, e.runs, cbases[t], e.cmax,
+    spmv_tile<T, NT, BETA>(tiles[t], e.rowptr, e.colidx, e.cidx, e.runs, cbases[t], poffs[t], e.cmax,
                            (const T *)e.vals, (const T *)e.x,
                            (T *)e.y, (T *)e.partials, alpha, beta, BETA, e.nnz, e.vector_ok, lds,
                            wsum, rp_lds, hl, fuse);
@@ -689,7 +754,7 @@ static hipError_t launch_spmv_batch(const SpmvBatchArgs &a, hipStream_t s) {
                               : (swz ? spmv_tiles_batch<T, false, false, true>
                                      : spmv_tiles_batch<T, false, false, false>));
         hipLaunchKernelGGL(kern, dim3(ntiles), dim3(kSpmvThreads), 0, s, a.entries, a.tiles,
-                           a.cbases, a.tiles_at, alpha, beta, fuse);
+                           a.cbases, a.poffs, a.tiles_at, alpha, beta, fuse);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -723,7 +788,7 @@ static hipError_t launch_spmv(const SpmvArgs &a, hipStream_t s) {
                                 : (bnz ? spmv_tiles<T, true, true> : spmv_tiles<T, true, false>);
     hipLaunchKernelGGL(kern, dim3(a.nblocks), dim3(kSpmvThreads), 0, s, a.rowptr, a.colidx,
                        (const T *)a.vals, (const T *)a.x, (T *)a.y, a.blocks, a.nblocks, a.cbases,
-                       a.cidx, a.runs, a.cmax, (T *)a.partials, alpha, beta, bnz, a.nnz, a.vector_ok, fuse);
+                       a.poffs, a.cidx, a.runs, a.cmax, (T *)a.partials, alpha, beta, bnz, a.nnz, a.vector_ok, fuse);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.nlong > 0 && !fuse) {

@@ -192,6 +192,25 @@ class SpMat:
             pass
 
 
+PLAN_STATS = ("tiles", "packed_tiles", "packed_entries", "schedule_bytes", "rowptr_bytes", "staged_tiles",
+              "index_bytes", "packed_rowoff_bytes")
+
+
+def spmv_plan_stats(rowptr, colidx, fp32: bool = False, nnz: int | None = None) -> dict:
+    """What one SpMV over the schedule of a HOST pattern reads besides the
+    values, x and y (rsp_spmv_plan_stats; no device needed). RSP_SPMV_PACK in
+    the environment selects the packed records, as for every schedule."""
+    import numpy as np
+
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    out = (C.c_int64 * len(PLAN_STATS))()
+    check(rsp.rsp_spmv_plan_stats(len(rp) - 1, rp.ctypes.data, ci.ctypes.data,
+                                  int(nnz if nnz is not None else len(ci)), 1 if fp32 else 0, out),
+          "rsp_spmv_plan_stats")
+    return dict(zip(PLAN_STATS, (int(v) for v in out)))
+
+
 class SpmvBatch:
     """Several independent products y_j = alpha*A_j*x_j (+ beta*y_j) as one
     launch (rsp_spmv_batch_*): the same bits per matrix as SpMat.spmv /
