@@ -98,7 +98,10 @@ int rsp_get_version(void);
 rsp_status_t rsp_create_csr(rsp_spmat_t *mat, int64_t rows, int64_t cols, int64_t nnz,
                             void *d_row_offsets, void *d_col_ind, void *d_values,
                             rsp_datatype_t value_type);
-/* Re-point the values array (e.g. fp64 -> fp32 copy) keeping the analysis. */
+/* Re-point the values array (e.g. fp64 -> fp32 copy) keeping the analysis:
+ * the schedule stays for the same value_type; another type re-plans on the next
+ * bufferSize / preprocess / SpMV (a tile's capacity depends on the type).
+ * INVALID_VALUE: a NULL mat, a value_type outside the enum. */
 rsp_status_t rsp_csr_set_values(rsp_spmat_t mat, void *d_values, rsp_datatype_t value_type);
 rsp_status_t rsp_destroy_spmat(rsp_spmat_t mat); /* cusparseDestroySpMat (GPU/spmv.cu:279) */
 
@@ -128,7 +131,9 @@ rsp_status_t rsp_spmv_preprocess(rsp_handle_t handle, rsp_operation_t op, const 
                                  rsp_datatype_t compute_type, void *d_buffer);
 /* cusparseSpMV (GPU/spmv.cu:179-186): y = alpha * A * x + beta * y.
  * op must be NON_TRANSPOSE (the only form the reference uses). If *beta == 0,
- * y is write-only. compute_type must equal the matrix value type. Deterministic:
+ * y is write-only. compute_type must equal the matrix value type (here and in
+ * bufferSize / preprocess / rsp_spmv_part / rsp_spmv_batch_create: INVALID_VALUE
+ * otherwise, e.g. a type left over from before rsp_csr_set_values). Deterministic:
  * the same inputs give bitwise identical y on every call. `d_buffer` is
  * accepted for signature parity and unused. Calls on one matrix must be
  * stream-ordered (its long-row tickets live in its schedule). */

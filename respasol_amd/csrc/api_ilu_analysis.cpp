@@ -609,10 +609,13 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
     up_step("arena build");
     hipError_t e = ar.commit(&f->d_arena, h->stream);
     up_step("commit (H2D)");
-    if (e == hipSuccess) e = hipMemsetD32(f->d_zero, INT_MAX, 1);
-    if (e == hipSuccess) e = hipMemsetD32(f->d_zero + 1, 0, 7);
-    if (e == hipSuccess) e = hipMemsetD32(f->d_fdone, 0, (size_t)std::max(n, 1));
-    if (e == hipSuccess) e = hipMemsetD32(f->d_tk, 0, 2 * rsp::kFlowTicketCtrs);
+    // on the handle's stream like everything else (the call is host-blocking:
+    // the counters are in place when it returns, whatever stream comes next)
+    if (e == hipSuccess) e = hipMemsetD32Async(f->d_zero, INT_MAX, 1, h->stream);
+    if (e == hipSuccess) e = hipMemsetD32Async(f->d_zero + 1, 0, 7, h->stream);
+    if (e == hipSuccess) e = hipMemsetD32Async(f->d_fdone, 0, (size_t)std::max(n, 1), h->stream);
+    if (e == hipSuccess) e = hipMemsetD32Async(f->d_tk, 0, 2 * rsp::kFlowTicketCtrs, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     f->tk_seq = 0;
     f->fac_gen = 0;
     f->claim_host = 0;

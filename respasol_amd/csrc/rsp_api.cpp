@@ -524,7 +524,7 @@ rsp_status_t rsp_api::spmv_run(rsp_handle_t h, rsp_operation_t op, const void *a
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!mat || !alpha || !beta) return RSP_STATUS_INVALID_VALUE;
     if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
-    if (compute_type != mat->type) return RSP_STATUS_NOT_SUPPORTED;
+    if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
     if (mat->rows > 0 && (!d_y || (mat->cols > 0 && !d_x))) return RSP_STATUS_INVALID_VALUE;
     (void)d_buffer;  // the schedule lives in the matrix (struct rsp_spmat)
     if (!mat->planned || mat->plan_type != compute_type) {  // lazily, if bufferSize was skipped
@@ -608,7 +608,7 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     for (int j = 0; j < count; j++) {
         rsp_spmat_t A = mats[j];
         if (!A) return RSP_STATUS_INVALID_VALUE;
-        if (A->type != compute_type) return RSP_STATUS_NOT_SUPPORTED;
+        if (A->type != compute_type) return RSP_STATUS_INVALID_VALUE;
         if (A->rows > 0 && (!d_y[j] || (A->cols > 0 && !d_x[j]))) return RSP_STATUS_INVALID_VALUE;
         if (!A->planned || A->plan_type != compute_type) {
             rsp_status_t st = spmv_plan(h, A, compute_type);
@@ -795,7 +795,11 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     }
     // the image is value-initialised, so every member's long-row partials and
     // tickets go up as 0 (tickets start, and stay, at 0 between launches)
-    if (bytes > 0) RSP_CHECK_HIP(hipMemcpy(b->d_mem, host.data(), bytes, hipMemcpyHostToDevice));
+    // (on the handle's stream; create is host-blocking and `host` is freed on return)
+    if (bytes > 0) {
+        RSP_CHECK_HIP(hipMemcpyAsync(b->d_mem, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+    }
     for (int j = 0; j < count; j++) {
         b->mats.push_back(mats[j]);
         b->plan_gen.push_back(mats[j]->plan_gen);
@@ -1108,7 +1112,7 @@ rsp_status_t rsp_spmv_buffer_size(rsp_handle_t h, rsp_operation_t op, const void
         if (!h) return RSP_STATUS_NOT_INITIALIZED;
         if (!mat || !buffer_size) return RSP_STATUS_INVALID_VALUE;
         if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
-        if (compute_type != mat->type) return RSP_STATUS_NOT_SUPPORTED;
+        if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
         // the schedule is built here, into the matrix's own device memory (the
         // reference calls bufferSize once, before its timed loop); the caller's
         // workspace is not needed
@@ -1130,7 +1134,7 @@ rsp_status_t rsp_spmv_preprocess(rsp_handle_t h, rsp_operation_t op, const void 
         if (!h) return RSP_STATUS_NOT_INITIALIZED;
         if (!mat) return RSP_STATUS_INVALID_VALUE;
         if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
-        if (compute_type != mat->type) return RSP_STATUS_NOT_SUPPORTED;
+        if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
         return spmv_plan(h, mat, compute_type);  // explicit request: always re-plan
     });
 }

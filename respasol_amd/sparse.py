@@ -156,6 +156,19 @@ class SpMat:
         call.keep = keep
         return call
 
+    def set_values(self, values: torch.Tensor) -> None:
+        """Re-point the values array, of either type (rsp_csr_set_values): the
+        schedule is kept for the same type and rebuilt by the next call for
+        another; batches created before hold the old pointer and become stale.
+        The tensor is kept alive."""
+        if values.dtype not in _DT:
+            raise TypeError("values must be float64 or float32")
+        if values.numel() < self.nnz_stored:
+            raise ValueError("values is shorter than the pattern")
+        check(rsp.rsp_csr_set_values(self._mat, _ptr(values), _DT[values.dtype]), "rsp_csr_set_values")
+        self.values = values
+        self.dtype = values.dtype
+
     def set_local_cols(self, ncols_local: int) -> None:
         """Split the schedule for halo overlap (rsp_spmat_set_local_cols): tiles
         reading columns < ncols_local only (the rank's own x) run as part 1."""

@@ -118,6 +118,33 @@ def test_level_path_still_selectable(handle, monkeypatch):
     assert np.array_equal(y, ob.trsv("lower_t", A.rowptr, A.colidx, rv, z))
 
 
+@pytest.mark.parametrize("alpha", [1.0, -0.75])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_default_plan_deep_dag_true_lu(handle, dtype, alpha):
+    """What both Krylov solvers run on a deep DAG with the default knobs: the
+    block-inverse L solve feeding the level-scheduled U solve (U has no block
+    plan). z is the block-order oracle's, y the oracle's U solve of that z,
+    bit for bit."""
+    A = csr.surrogate("dc1", 0.2)
+    x, _ = csr.dlarnv(2, [0, 0, 0, 1], A.n)
+    xx = np.ascontiguousarray(x, NP[dtype])
+    rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values, dtype)
+    il = Ilu0(handle, rp, ci, nnz=A.nnz)
+    il.analysis()
+    il.factor(va)
+    assert il.zero_pivot() == -1
+    z = il.solve_lower(va, torch.from_numpy(xx).cuda(), alpha=alpha)
+    y = il.solve_upper(va, z, alpha=alpha)
+    assert il.solve_zero_pivot(il.TRSV_L) == -1 and il.solve_zero_pivot(il.TRSV_U) == -1
+    assert il.solve_blocks()[0] > 0
+    rv, sz, zp = ob.ilu0(A.rowptr, A.colidx, A.values.astype(NP[dtype]))
+    assert sz == -1 and zp == -1 and np.array_equal(va.cpu().numpy(), rv)
+    rz = ob.trsv("lower_n_blocks", A.rowptr, A.colidx, rv, xx, alpha=alpha)
+    assert np.array_equal(z.cpu().numpy(), rz), f"L solve: {np.count_nonzero(z.cpu().numpy() != rz)} differ"
+    ry = ob.trsv("upper", A.rowptr, A.colidx, rv, rz, alpha=alpha)
+    assert np.array_equal(y.cpu().numpy(), ry), f"U solve: {np.count_nonzero(y.cpu().numpy() != ry)} differ"
+
+
 def test_solve_reads_the_values_it_is_given(handle):
     """The coefficients are built by each solve from its own values argument:
     a second factor of changed values, then the solves, use the new ones."""

@@ -38,7 +38,7 @@ def handle():
     h.close()
 
 
-def gpu_ilu(handle, A, dtype, ftz=False, x=None, true_lu=False):
+def gpu_ilu(handle, A, dtype, ftz=False, x=None, true_lu=False, alpha=1.0):
     handle.set_ftz(ftz)
     rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values, dtype)
     il = Ilu0(handle, rp, ci, nnz=A.nnz)
@@ -50,8 +50,8 @@ def gpu_ilu(handle, A, dtype, ftz=False, x=None, true_lu=False):
     il.factor(va)
     zp = il.zero_pivot()
     xx = torch.from_numpy(np.ascontiguousarray(x if x is not None else np.ones(A.n), NP[dtype])).cuda()
-    z = il.solve_lower(va, xx)
-    y = il.solve_upper(va, z) if true_lu else il.solve_lower(va, z, transpose=True)
+    z = il.solve_lower(va, xx, alpha=alpha)
+    y = il.solve_upper(va, z, alpha=alpha) if true_lu else il.solve_lower(va, z, transpose=True, alpha=alpha)
     torch.cuda.synchronize()
     assert il.zero_pivot() == zp  # (raises if the factor's flow launch gave up waiting)
     assert il.solve_zero_pivot(il.TRSV_L) == -1  # (raise if a solve's flow launch gave up)
@@ -60,17 +60,17 @@ def gpu_ilu(handle, A, dtype, ftz=False, x=None, true_lu=False):
     return va.cpu().numpy(), zp, z.cpu().numpy(), y.cpu().numpy(), il
 
 
-def oracle_ilu(A, dtype, ftz=False, x=None, true_lu=False):
+def oracle_ilu(A, dtype, ftz=False, x=None, true_lu=False, alpha=1.0):
     v, sz, zp = ob.ilu0(A.rowptr, A.colidx, A.values.astype(NP[dtype]), ftz=ftz)
     xx = np.ascontiguousarray(x if x is not None else np.ones(A.n), NP[dtype])
-    z = ob.trsv("lower_n", A.rowptr, A.colidx, v, xx, ftz=ftz)
-    y = ob.trsv("upper" if true_lu else "lower_t", A.rowptr, A.colidx, v, z, ftz=ftz)
+    z = ob.trsv("lower_n", A.rowptr, A.colidx, v, xx, alpha=alpha, ftz=ftz)
+    y = ob.trsv("upper" if true_lu else "lower_t", A.rowptr, A.colidx, v, z, alpha=alpha, ftz=ftz)
     return v, sz, zp, z, y
 
 
-def compare(A, dtype, handle, ftz=False, x=None, true_lu=False):
-    v, zp, z, y, il = gpu_ilu(handle, A, dtype, ftz, x, true_lu)
-    rv, rsz, rzp, rz, ry = oracle_ilu(A, dtype, ftz, x, true_lu)
+def compare(A, dtype, handle, ftz=False, x=None, true_lu=False, alpha=1.0):
+    v, zp, z, y, il = gpu_ilu(handle, A, dtype, ftz, x, true_lu, alpha)
+    rv, rsz, rzp, rz, ry = oracle_ilu(A, dtype, ftz, x, true_lu, alpha)
     assert rsz == -1 and zp == rzp
     ftol, stol = TOL[dtype]
     scale = np.maximum(np.abs(rv.astype(np.float64)), 1e-300)
@@ -264,6 +264,34 @@ def test_fat_level_paths(handle, monkeypatch, slot, lds, pad, wlds, flong, name,
     x, _ = csr.dlarnv(2, [0, 0, 0, 1], A.n)
     compare(A, torch.float64, handle, x=x)
     compare(A, torch.float32, handle, x=x)
+
+
+_THIN = ("RSP_ILU_THIN_SOLVE", "RSP_ILU_THIN_FACTOR")
+_FAT = ("RSP_ILU_FAT_SLOT", "RSP_ILU_FAT_LDS", "RSP_ILU_FAT_PAD", "RSP_ILU_WAVE_LDS", "RSP_ILU_FAT_LONG") + _THIN
+# the three schedules of test_schedule_variants, the first and last parameter sets of test_fat_level_paths
+ALPHA_PATHS = ([(name, scale, dict(zip(_THIN, knobs))) for knobs in ((0, 0), (1024, 1 << 30), (1, 1))
+                for name, scale in (("stomach", 0.05), ("G2_circuit", 0.2))]
+               + [("crashbasis", 0.1, dict(zip(_FAT, knobs + (0, 0)))) for knobs in ((0, 1, 0, 0, 3), (1, 1, 0, 1, 1))])
+
+
+@pytest.mark.parametrize("alpha", [-0.75, 2.0 ** -30])
+@pytest.mark.parametrize("name,scale,knobs", ALPHA_PATHS,
+                         ids=[f"{n}-{'-'.join(str(v) for v in k.values())}" for n, _, k in ALPHA_PATHS])
+def test_solve_alpha(handle, monkeypatch, name, scale, knobs, alpha):
+    """L y = alpha x, L^T y = alpha x and U y = alpha x with alpha != 1 on the
+    level-scheduled paths (thin runs, level launches, flow runs, fat levels):
+    alpha multiplies x once, in the type of the solve (trsv_stream), before
+    any term is subtracted — bitwise the oracle's, for an alpha that changes
+    sign and mantissa (-0.75: a rounding per element) and one that only moves
+    the exponent (2^-30: exact, so a second or a missing multiplication
+    cannot hide in rounding); fp64, fp32 and fp32+FTZ."""
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, str(v))
+    A = csr.surrogate(name, scale)
+    x, _ = csr.dlarnv(2, [0, 0, 0, 1], A.n)
+    for dtype, ftz in ((torch.float64, False), (torch.float32, False), (torch.float32, True)):
+        for true_lu in (False, True):
+            compare(A, dtype, handle, ftz=ftz, x=x, true_lu=true_lu, alpha=alpha)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -639,6 +667,32 @@ def test_flow_give_up_is_recovered(handle, monkeypatch, dtype, ftz):
     assert il.solve_zero_pivot(il.TRSV_L) == -1
     assert il.solve_zero_pivot(il.TRSV_LT) == -1
     rv, _, _, rz, ry = oracle_ilu(A, dtype, ftz=ftz)
+    assert np.array_equal(va.cpu().numpy(), rv)
+    assert np.array_equal(z.cpu().numpy(), rz) and np.array_equal(y.cpu().numpy(), ry)
+
+
+def test_flow_give_up_recovery_keeps_alpha(handle, monkeypatch):
+    """test_flow_give_up_is_recovered with alpha = -0.75 on both solves (fp64):
+    the recovery re-runs a recorded solve with the alpha of that call
+    (SolveCall::alpha), not 1 — for the L solve and for the L^T solve made
+    after it, which the L solve's recovery re-runs too."""
+    alpha = -0.75
+    monkeypatch.setenv("RSP_ILU_THIN_FACTOR", "0")
+    monkeypatch.setenv("RSP_ILU_THIN_SOLVE", "0")
+    monkeypatch.setenv("RSP_ILU_FLOW_TIMEOUT_US", "0")
+    monkeypatch.setenv("RSP_ILU_FAC_ONE", "0")  # the factor's flow runs (see above)
+    A = csr.surrogate("G2_circuit", 0.1)
+    rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
+    il = Ilu0(handle, rp, ci, nnz=A.nnz)
+    il.analysis()
+    ones = torch.ones(A.n, dtype=torch.float64, device="cuda")
+    il.factor(va)
+    assert il.zero_pivot() == -1
+    z = il.solve_lower(va, ones, alpha=alpha)
+    y = il.solve_lower(va, z, transpose=True, alpha=alpha)
+    assert il.solve_zero_pivot(il.TRSV_L) == -1
+    assert il.solve_zero_pivot(il.TRSV_LT) == -1
+    rv, _, _, rz, ry = oracle_ilu(A, torch.float64, alpha=alpha)
     assert np.array_equal(va.cpu().numpy(), rv)
     assert np.array_equal(z.cpu().numpy(), rz) and np.array_equal(y.cpu().numpy(), ry)
 

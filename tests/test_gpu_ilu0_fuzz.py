@@ -3,7 +3,8 @@ reproducible): random patterns — banded, random, clustered, with hub rows
 and columns and with deep chains — and strictly diagonally dominant values;
 the factor, the L solve and the L^T solve are checked bit for bit against
 the oracle (reference operation order), fp64 and fp32, under the shipped
-schedule and with every level forced fat (flow launches everywhere)."""
+schedule and with every level forced fat (flow launches everywhere); a
+second pass runs L then the U solve with both alphas off 1."""
 import numpy as np
 import pytest
 import torch
@@ -87,5 +88,39 @@ def test_random_patterns_bitwise(monkeypatch, dtype, fat, lower):
         assert np.array_equal(va.cpu().numpy(), v), (seed, "factor")
         assert np.array_equal(z.cpu().numpy(), rz), (seed, "L")
         assert np.array_equal(y.cpu().numpy(), ry), (seed, "L^T")
+        del il
+    h.close()
+
+
+@pytest.mark.parametrize("fat", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_random_patterns_true_lu_with_alpha(monkeypatch, dtype, fat):
+    """The same matrices through the true ILU(0) apply with both scalars off
+    1: L z = -0.75 x, then U y = 1.5 z (the U solve divides by the factor's
+    diagonal), bit for bit the oracle's, under the shipped schedule and with
+    every level fat."""
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    if fat:
+        monkeypatch.setenv("RSP_ILU_THIN_FACTOR", "0")
+        monkeypatch.setenv("RSP_ILU_THIN_SOLVE", "0")
+    h = Handle()
+    for seed in SEEDS:
+        A = random_matrix(seed)
+        v, sz, zp = ob.ilu0(A.rowptr, A.colidx, A.values.astype(NP[dtype]))
+        assert sz == -1 and zp == -1
+        x = np.random.default_rng(seed).uniform(-1, 1, A.n).astype(NP[dtype])
+        rz = ob.trsv("lower_n", A.rowptr, A.colidx, v, x, alpha=-0.75)
+        ry = ob.trsv("upper", A.rowptr, A.colidx, v, rz, alpha=1.5)
+        rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values, dtype)
+        il = Ilu0(h, rp, ci, nnz=A.nnz)
+        il.analysis()
+        il.factor(va)
+        assert il.zero_pivot() == -1
+        z = il.solve_lower(va, torch.from_numpy(x).cuda(), alpha=-0.75)
+        y = il.solve_upper(va, z, alpha=1.5)
+        assert il.solve_zero_pivot(il.TRSV_L) == -1 and il.solve_zero_pivot(il.TRSV_U) == -1
+        assert np.array_equal(va.cpu().numpy(), v), (seed, "factor")
+        assert np.array_equal(z.cpu().numpy(), rz), (seed, "L")
+        assert np.array_equal(y.cpu().numpy(), ry), (seed, "U")
         del il
     h.close()

@@ -108,3 +108,31 @@ def test_plan_no_staging_past_the_x_resource(shift, staged64, staged32):
         st, tiles, e16, est = plan(A, dt)
         assert st == 0 and e16 == len(ci)
         assert (est > 0.9 * len(ci)) if want else est == 0
+
+
+def test_rectangular_fuzz_matrices_cover_every_tile_kind():
+    """The rectangular matrices of tests/test_gpu_spmv_fuzz.py
+    (random_rect_matrix) plan consistently and, taken together, hold every
+    kind of tile the GPU test is there for — so a change of the generator
+    cannot silently stop covering one: 16-bit tiles, int32 tiles (spanning
+    >= 65536 columns), staged tiles, chunks of a row longer than a tile; and
+    the slice-shaped matrix has 16-bit entries of gathered (not staged) tiles
+    in columns past its row count, where a clamp to rows - 1 would show."""
+    from oracle_bind import TILE_CAP
+    from test_gpu_spmv_fuzz import RECT_SEEDS, RECT_SHAPES, random_rect_matrix
+    for dt, npdt in ((R64, np.float64), (R32, np.float32)):
+        n16 = n32 = nstaged = nlong = 0
+        for seed in RECT_SEEDS:
+            A = random_rect_matrix(seed)
+            assert (A.m, A.n) == RECT_SHAPES[seed]
+            assert A.colidx.size == 0 or (A.colidx.min() >= 0 and A.colidx.max() < A.n)
+            st, tiles, e16, est = plan(A, dt)
+            assert st == 0 and 0 <= est <= e16 <= A.nnz_stored
+            assert tiles > 0 or A.nnz_stored == 0
+            n16 += e16
+            n32 += A.nnz_stored - e16
+            nstaged += est
+            nlong += int(np.count_nonzero(np.diff(A.rowptr) > TILE_CAP[np.dtype(npdt)]))
+            if RECT_SHAPES[seed] == (6000, 66000):
+                assert e16 - est > 0 and np.count_nonzero(A.colidx >= A.m) > A.nnz_stored // 2
+        assert n16 > 0 and n32 > 0 and nstaged > 0 and nlong > 0, (dt, n16, n32, nstaged, nlong)
