@@ -215,7 +215,10 @@ rsp_status_t rsp_trsv_zero_pivot(rsp_handle_t handle, rsp_ilu0_info_t info, int 
 /* cusparse?csrilu02 (GPU/ilu0.cu:264-268): in-place ILU(0) on the CSR
  * pattern, IKJ order: for each row i, for each k < i in the pattern
  * (ascending): a_ik /= u_kk; a_ij -= a_ik * u_kj for j > k in both rows.
- * value_type selects fp64 or fp32 arithmetic (FTZ per handle mode). */
+ * value_type selects fp64 or fp32 arithmetic (FTZ per handle mode). Like
+ * csrilu02, the factor completes after a zero pivot with IEEE inf / NaN
+ * propagation (x / 0 = +-inf, inf - inf = NaN), and rsp_ilu0_zero_pivot then
+ * reports the smallest row j with U(j,j) == 0, whatever the schedule. */
 rsp_status_t rsp_ilu0_factor(rsp_handle_t handle, rsp_ilu0_info_t info, rsp_datatype_t value_type,
                              void *d_values);
 

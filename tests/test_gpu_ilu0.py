@@ -55,7 +55,10 @@ def gpu_ilu(handle, A, dtype, ftz=False, x=None, true_lu=False, alpha=1.0):
     torch.cuda.synchronize()
     assert il.zero_pivot() == zp  # (raises if the factor's flow launch gave up waiting)
     assert il.solve_zero_pivot(il.TRSV_L) == -1  # (raise if a solve's flow launch gave up)
-    il.solve_zero_pivot(il.TRSV_U if true_lu else il.TRSV_LT)
+    if true_lu:
+        assert il.solve_zero_pivot(il.TRSV_U) == zp  # U divides by the pivots: the factor's report
+    else:
+        assert il.solve_zero_pivot(il.TRSV_LT) == -1
     handle.set_ftz(False)
     return va.cpu().numpy(), zp, z.cpu().numpy(), y.cpu().numpy(), il
 
@@ -562,10 +565,12 @@ def test_flow_segments(handle, monkeypatch, flow, wpc, mode, name, scale):
 @pytest.mark.parametrize("exp2", [0, 70, -70, 100])
 @pytest.mark.parametrize("name,scale", [("dc1", 0.05), ("xenon2", 0.1)])
 def test_ftz_division_any_exponent(handle, exp2, name, scale):
-    """FTZ build divisions (ilu0.hip qdiv): operands within [2^-60, 2^60] run
-    the float Newton sequence without the denormal-mode switch, others the
-    double quotient rounded once; with the matrix scaled by 2^exp2 both
-    branches meet the oracle's DAZ/FTZ bits (factor and solves, fp32)."""
+    """FTZ build divisions (ilu0.hip qdiv): every float division takes the
+    quotient of the operands widened to double, rounded once to float, which
+    is the correctly rounded float quotient whatever the exponents; with the
+    whole matrix scaled by 2^exp2 (so no operand is denormal) it meets the
+    oracle's DAZ/FTZ bits (factor and solves, fp32). Denormal operands are
+    tests/test_gpu_ilu0_zero_pivot.py."""
     import dataclasses
     A = csr.surrogate(name, scale)
     A = dataclasses.replace(A, values=A.values * (2.0 ** exp2))
