@@ -130,8 +130,17 @@ rsp_status_t rsp_spmv_preprocess(rsp_handle_t handle, rsp_operation_t op, const 
                                  rsp_spmat_t mat, const void *d_x, const void *beta, void *d_y,
                                  rsp_datatype_t compute_type, void *d_buffer);
 /* cusparseSpMV (GPU/spmv.cu:179-186): y = alpha * A * x + beta * y.
- * op must be NON_TRANSPOSE (the only form the reference uses). If *beta == 0,
- * y is write-only. compute_type must equal the matrix value type (here and in
+ * op must be NON_TRANSPOSE (the only form the reference uses). The rounding
+ * is fixed: with T the compute type and s the row's products summed in the
+ * canonical order (spmv.hip; oracle_spmv_canon_* of oracle/rsp_oracle.h),
+ *     y = round(round(alpha * s) + round(beta * y)),
+ * each round() to T: two rounded products and one rounded sum, never a fused
+ * multiply-add, never a wider type, alpha applied once to the whole row's sum
+ * (also for a row cut into chunks); an empty row has s = +0. If *beta == 0,
+ * of either sign, y is write-only: it is not read (a NaN in it is ignored) and
+ * y = round(alpha * s). rsp_spmv_part and rsp_spmv_batch_run follow the same
+ * rule, so parts and batches are bit for bit equal to the single call
+ * (tests/spmv_epilogue_ref.py restates it). compute_type must equal the matrix value type (here and in
  * bufferSize / preprocess / rsp_spmv_part / rsp_spmv_batch_create: INVALID_VALUE
  * otherwise, e.g. a type left over from before rsp_csr_set_values). Deterministic:
  * the same inputs give bitwise identical y on every call. `d_buffer` is

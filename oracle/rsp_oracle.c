@@ -84,6 +84,20 @@ void oracle_set_threads(int t) { omp_set_num_threads(t > 0 ? t : 1); }
  *    combined by a xor-butterfly tree (stride 32, 16, ..., 1) and the four
  *    results as (w0+w1)+(w2+w3); the chunks are added in order from 0. */
 #define ORACLE_CANON(T, NAME)                                                                  \
+    /* one chunk of a long row: entries [k0, k1) of v / ci */                                  \
+    static T NAME##_chunk(const int *ci, const T *v, const T *x, int k0, int k1) {             \
+        T q[256];                                                                              \
+        for (int t = 0; t < 256; t++) q[t] = 0;                                                \
+        for (int k = k0; k < k1; k++) q[(k - k0) & 255] += v[k] * x[ci[k]];                    \
+        T w[4];                                                                                \
+        for (int g = 0; g < 4; g++) {                                                          \
+            T *qq = q + 64 * g;                                                                \
+            for (int o = 32; o >= 1; o >>= 1)                                                  \
+                for (int l = 0; l < o; l++) qq[l] = qq[l] + qq[l + o];                         \
+            w[g] = qq[0];                                                                      \
+        }                                                                                      \
+        return (w[0] + w[1]) + (w[2] + w[3]);                                                  \
+    }                                                                                          \
     void NAME(int m, const int *rp, const int *ci, const T *v, const T *x, T *y, int cap) {    \
         for (int i = 0; i < m; i++) {                                                          \
             const int a = rp[i], len = rp[i + 1] - rp[i];                                      \
@@ -96,22 +110,21 @@ void oracle_set_threads(int t) { omp_set_num_threads(t > 0 ? t : 1); }
                 continue;                                                                      \
             }                                                                                  \
             T row = 0;                                                                         \
-            for (int c0 = 0; c0 < len; c0 += cap) {                                            \
-                const int c1 = c0 + cap < len ? c0 + cap : len;                                \
-                T q[256];                                                                      \
-                for (int t = 0; t < 256; t++) q[t] = 0;                                        \
-                for (int e = c0; e < c1; e++) q[(e - c0) & 255] += v[a + e] * x[ci[a + e]];     \
-                T w[4];                                                                        \
-                for (int g = 0; g < 4; g++) {                                                  \
-                    T *qq = q + 64 * g;                                                        \
-                    for (int o = 32; o >= 1; o >>= 1)                                          \
-                        for (int l = 0; l < o; l++) qq[l] = qq[l] + qq[l + o];                 \
-                    w[g] = qq[0];                                                              \
-                }                                                                              \
-                row += (w[0] + w[1]) + (w[2] + w[3]);                                          \
-            }                                                                                  \
+            for (int c0 = 0; c0 < len; c0 += cap)                                              \
+                row += NAME##_chunk(ci, v, x, a + c0, a + (c0 + cap < len ? c0 + cap : len));  \
             y[i] = row;                                                                        \
         }                                                                                      \
+    }                                                                                          \
+    /* the chunk partials of row i (a row of > 256 products): part[c], c < ceil(len / cap), */ \
+    /* which NAME adds in order from 0; returns their count, 0 for a shorter row */            \
+    int NAME##_partials(const int *rp, const int *ci, const T *v, const T *x, int i, int cap,  \
+                        T *part) {                                                             \
+        const int a = rp[i], len = rp[i + 1] - rp[i];                                          \
+        int n = 0;                                                                             \
+        if (len <= 256) return 0;                                                              \
+        for (int c0 = 0; c0 < len; c0 += cap)                                                  \
+            part[n++] = NAME##_chunk(ci, v, x, a + c0, a + (c0 + cap < len ? c0 + cap : len)); \
+        return n;                                                                              \
     }
 ORACLE_CANON(double, oracle_spmv_canon_f64)
 ORACLE_CANON(float, oracle_spmv_canon_f32)

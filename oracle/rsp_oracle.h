@@ -56,6 +56,14 @@ void oracle_spmv_canon_f32(int m, const int *rowptr, const int *colidx, const fl
 void oracle_spmv_canon_f32_ftz(int m, const int *rowptr, const int *colidx, const float *vals,
                                const float *x, float *y, int cap);
 
+/* The chunk partials of row i as the canonical order forms them (a row of more
+ * than 256 products; `part` holds ceil(len / cap) values): oracle_spmv_canon_*
+ * adds them in order from 0. Returns their count, 0 for a shorter row. */
+int oracle_spmv_canon_f64_partials(const int *rowptr, const int *colidx, const double *vals,
+                                   const double *x, int row, int cap, double *part);
+int oracle_spmv_canon_f32_partials(const int *rowptr, const int *colidx, const float *vals,
+                                   const float *x, int row, int cap, float *part);
+
 /* In-place ILU(0), IKJ, fma updates (cusparse?csrilu02, GPU/ilu0.cu:264-268).
  * Returns the first structurally missing diagonal (>= 0) without factoring,
  * else -1; *zero_pivot = smallest i with u_ii == 0 after the factor, or -1. */

@@ -27,6 +27,9 @@ def _load():
     for name in ("oracle_spmv_canon_f64", "oracle_spmv_canon_f32", "oracle_spmv_canon_f32_ftz"):
         getattr(lib, name).argtypes = [C.c_int, ip, ip, vp, vp, vp, C.c_int]
         getattr(lib, name).restype = None
+    for name in ("oracle_spmv_canon_f64_partials", "oracle_spmv_canon_f32_partials"):
+        getattr(lib, name).argtypes = [ip, ip, vp, vp, C.c_int, C.c_int, vp]
+        getattr(lib, name).restype = C.c_int
     lib.oracle_num_threads.restype = C.c_int
     lib.oracle_set_threads.argtypes = [C.c_int]
     lib.oracle_set_threads.restype = None
@@ -81,6 +84,22 @@ def spmv(rowptr, colidx, vals, x, ftz=False, threads=False, order="seq"):
     fn(m, rp.ctypes.data_as(C.POINTER(C.c_int)), ci.ctypes.data_as(C.POINTER(C.c_int)),
        v.ctypes.data, xx.ctypes.data, y.ctypes.data)
     return y
+
+
+def spmv_canon_partials(rowptr, colidx, vals, x, row):
+    """The chunk partials of a row longer than 256 entries, as the canonical
+    order forms them (spmv(..., order="canon") adds them in order from 0); an
+    empty array for a shorter row."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    v = np.ascontiguousarray(vals)
+    xx = np.ascontiguousarray(x, v.dtype)
+    cap = TILE_CAP[v.dtype]
+    part = np.empty((int(rp[row + 1] - rp[row]) + cap - 1) // cap + 1, v.dtype)
+    fn = lib.oracle_spmv_canon_f64_partials if v.dtype == np.float64 else lib.oracle_spmv_canon_f32_partials
+    n = fn(rp.ctypes.data_as(C.POINTER(C.c_int)), ci.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data,
+           xx.ctypes.data, int(row), cap, part.ctypes.data)
+    return part[:n].copy()
 
 
 def ilu0(rowptr, colidx, vals, ftz=False):

@@ -17,6 +17,7 @@ import torch
 import oracle_bind as ob
 from respasol_amd import csr
 from respasol_amd.sparse import Handle, SpMat, upload_csr
+from spmv_epilogue_ref import epilogue
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mtx")
@@ -203,9 +204,14 @@ def test_alpha_beta(handle):
     y, _, _ = run_gpu(handle, A, x, torch.float64, alpha=2.0, beta=-0.5, y0=y0)
     ref = 2.0 * ob.spmv(A.rowptr, A.colidx, A.values, x) - 0.5 * y0
     assert np.allclose(y, ref, rtol=1e-14, atol=1e-13)
-    # beta == 0 must not read y (NaN in y is ignored, cuSPARSE semantics)
+    canon = ob.spmv(A.rowptr, A.colidx, A.values, x, order="canon")
+    assert same_bits(y, epilogue(canon, y0, 2.0, -0.5))
+    # beta == 0 must not read y (NaN in y is ignored, cuSPARSE semantics): the
+    # bits of the same call on a clean y, which are the canonical sums
     y, _, _ = run_gpu(handle, A, x, torch.float64, beta=0.0, y0=np.full(A.m, np.nan))
+    clean, _, _ = run_gpu(handle, A, x, torch.float64, beta=0.0, y0=y0)
     assert np.all(np.isfinite(y))
+    assert same_bits(y, clean) and same_bits(y, canon)
 
 
 def test_unaligned_pointers_scalar_path(handle):
