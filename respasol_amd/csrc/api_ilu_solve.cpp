@@ -1,5 +1,5 @@
 // api_ilu_solve.cpp — the ILU(0) factor and the triangular solves of
-// include/rsp.h: the launches of the kernels in ilu0.hip / trsv_blocks.hip
+// include/rsp.h: the launches of the kernels in ilu0.hip / trsv.hip / trsv_blocks.hip
 // over the plans of api_ilu_analysis.cpp, and the recovery of a call whose
 // flow wait gave up (the two *_zero_pivot calls). Mirrors the factor and
 // solve calls of the reference driver (GPU/ilu0.cu:254-310).

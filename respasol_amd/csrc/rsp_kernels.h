@@ -315,7 +315,7 @@ struct FacFlowRun {
 //    wait they abandon (a flow item writes nothing before its waits).
 //    Every ticket is then held by a workgroup that has started, and the
 //    lowest unfinished item is its owner's next: progress needs no
-//    co-residency (ilu0.hip FlowClaims). The tickets come from eight
+//    co-residency (ilu_flow.h FlowClaims). The tickets come from eight
 //    counters of one of two slots (launch sequence number & 1), zeroed by
 //    the launch before;
 //  * static (RSP_ILU_FLOW_MODE=0): wave w of the grid takes items w, w + W, ... Progress
@@ -354,10 +354,7 @@ constexpr int kFlowClaims = 1;
 constexpr int kFlowTickets = 2;
 constexpr int kFlowTicketCtrs = 8;    // tickets: start-claim counters per launch
 constexpr int kFlowOwnMax = 1024;     // tickets: the most one workgroup can own (>= the largest flow grid)
-#ifndef RSP_TK_STEAL_US
-#define RSP_TK_STEAL_US 50
-#endif
-constexpr int kFlowStealUs = RSP_TK_STEAL_US;      // tickets: a wait this long may steal (2 us once the workgroup has)
+constexpr int kFlowStealUs = 50;      // tickets: a wait this long may steal (2 us once the workgroup has)
 
 
 struct IluArgs {

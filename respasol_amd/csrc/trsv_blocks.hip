@@ -1,7 +1,7 @@
 // trsv_blocks.hip — block-inverse solve of deep-DAG unit-lower triangles for
 // gfx950 (round 6): the L and L^T solves of cusparse?csrsv2_solve
 // (GPU/ilu0.cu:284-310) on DAGs of ~10^4 levels of ~10 rows (the circuits),
-// where the level-scheduled kernels of ilu0.hip pay one dependent hand-off
+// where the level-scheduled kernels of trsv.hip pay one dependent hand-off
 // per level (~190 ns) and lose to one CPU core.
 //
 // Plan (ilu_blocks.cpp, rsp::BlkDesc): the rows in level order ("positions")
@@ -32,7 +32,7 @@
 //                  out to HBM. No hand-off between waves, no atomics: the
 //                  only dependency chain is the wave's own LDS order;
 //   trsv_blk_out   y[row] = y by position.
-// Compiled twice like ilu0.hip (rsp_k / rsp_k_ftz).
+// Compiled twice like trsv.hip (rsp_k / rsp_k_ftz).
 
 #include <hip/hip_runtime.h>
 

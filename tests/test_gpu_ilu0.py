@@ -565,7 +565,7 @@ def test_flow_segments(handle, monkeypatch, flow, wpc, mode, name, scale):
 @pytest.mark.parametrize("exp2", [0, 70, -70, 100])
 @pytest.mark.parametrize("name,scale", [("dc1", 0.05), ("xenon2", 0.1)])
 def test_ftz_division_any_exponent(handle, exp2, name, scale):
-    """FTZ build divisions (ilu0.hip qdiv): every float division takes the
+    """FTZ build divisions (ilu_device.h qdiv): every float division takes the
     quotient of the operands widened to double, rounded once to float, which
     is the correctly rounded float quotient whatever the exponents; with the
     whole matrix scaled by 2^exp2 (so no operand is denormal) it meets the
