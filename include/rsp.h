@@ -451,7 +451,16 @@ rsp_status_t rsp_ilu0_levels(rsp_ilu0_info_t info, int *levels_lower, int *level
  * time forces it on / off) are solved block by block, each row's unknown
  * written as a combination of its block's right-hand sides and of earlier
  * blocks' unknowns: same unknowns, rounding of that order (restated in the
- * oracle), within SURVEY 8c's tolerance of the reference's order. */
+ * oracle), within SURVEY 8c's tolerance of the reference's order.
+ * LDS rule: the solve builds each block's coefficients in the LDS of one CU,
+ * the largest block staged whole. A DAG whose plan needs more than
+ * 160 KiB (163,840 B) there, counted for fp64 values as
+ *   8 * max over blocks (dependencies + 1 + pattern entries)
+ * + 4 * max over blocks (2 * pattern entries + 1 + recipe items + levels + 1),
+ * gets no block plan: 0 is reported for it and its solve is level-scheduled
+ * in the reference's order, for fp64 and fp32 alike. L and L^T are decided
+ * separately. A dense 64-row diagonal block or a full band of half-width 12
+ * are such patterns. */
 rsp_status_t rsp_ilu0_solve_blocks(rsp_ilu0_info_t info, int *blocks_lower, int *blocks_upper);
 
 /* Tests and profiling (no cuSPARSE counterpart, no device needed): the host

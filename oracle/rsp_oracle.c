@@ -426,6 +426,7 @@ static int cmp_int(const void *a, const void *b) {
 typedef struct {
     int nb;
     int *blk, *bstart, *islong; /* per position; per block (bstart[nb] = n) */
+    int *cst, *capcut;          /* per position: its chunk's first position; started by the lcap rule */
     long long *po;              /* per position: pattern offset, po[n] = total */
     int *nx;                    /* per position: x sources */
     int *pool;
@@ -436,16 +437,22 @@ static void blk_plan(int n, const int *ord, const BlkDeps *d, const int *prm, Bl
     for (int p = 0; p < n; p++) pos[ord[p]] = p;
     /* chunk starts: cst[p] = the first position of p's chunk */
     int *cst = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
+    int *capcut = (int *)calloc((size_t)(n > 0 ? n : 1), sizeof(int));
     for (int p = 0, c0 = 0; p < n; p++) {
         if (p - c0 == ch) c0 = p;
         else if (p > c0) {
             const int r = ord[p];
             int m = 0;
             for (int o = d->dp[r]; o < d->dp[r + 1]; o++) m += pos[d->dj[o]] >= c0;
-            if (m > lcap) c0 = p;
+            if (m > lcap) {
+                c0 = p;
+                capcut[p] = 1;
+            }
         }
         cst[p] = c0;
     }
+    P->cst = cst;
+    P->capcut = capcut;
     int *stamp = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
     for (int p = 0; p < n; p++) stamp[p] = -1;
     P->blk = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
@@ -530,9 +537,10 @@ static void blk_plan(int n, const int *ord, const BlkDeps *d, const int *prm, Bl
     free(ys.v);
     free(stamp);
     free(pos);
-    free(cst);
 }
 static void blk_free(BlkPlan *P, BlkDeps *d, int *ord) {
+    free(P->cst);
+    free(P->capcut);
     free(P->blk);
     free(P->bstart);
     free(P->islong);
@@ -611,6 +619,84 @@ static void blk_free(BlkPlan *P, BlkDeps *d, int *ord) {
     }
 ORACLE_BLOCKS(double, d, fma)
 ORACLE_BLOCKS(float, s, fmaf)
+
+/* Facts of the plan (rsp_oracle.h), from blk_plan alone. A row's FAR terms are
+ * its y sources before max(chunk start, block start - nw), the others are
+ * its in-chunk terms; a long block's rounds are ceil(in-chunk terms / 64). */
+int oracle_trsv_blocks_facts(int kind, int n, const int *rp, const int *ci, const int *params,
+                             long long *out) {
+    static const int dflt[6] = BLK_DEFAULTS;
+    const int *prm = params ? params : dflt;
+    if (n < 0 || kind < 0 || kind > 1 || prm[0] < 1 || prm[0] > 64 || prm[4] < 1 || !out) return -1;
+    for (int k = 0; k < ORACLE_BLK_FACTS; k++) out[k] = 0;
+    if (n == 0) return 0;
+    BlkDeps d;
+    blk_deps(kind, n, rp, ci, &d);
+    int *ord = blk_order(kind, n, &d);
+    BlkPlan P;
+    blk_plan(n, ord, &d, prm, &P);
+    int *pos = (int *)malloc((size_t)n * sizeof(int));
+    int *ilev = (int *)malloc((size_t)n * sizeof(int));
+    for (int p = 0; p < n; p++) pos[ord[p]] = p;
+    const int nw = prm[3];
+    long long elems = 0, words = 0;
+    int nch = 0;
+    out[0] = P.nb;
+    for (int b = 0; b < P.nb; b++) {
+        const int s = P.bstart[b], e = P.bstart[b + 1], c0 = P.cst[s];
+        const int thr = c0 > s - nw ? c0 : s - nw;
+        if (s == c0) {
+            nch++;
+            out[3] += P.capcut[s];
+        }
+        out[ORACLE_BLK_FACTS + nch - 1]++;
+        long long nd = 0, ne = P.po[e] - P.po[s], items = 0;
+        int nlev = 0, maxnear = 0;
+        for (int p = s; p < e; p++) {
+            const int r = ord[p];
+            long long nfar = 0;
+            for (long long k = P.po[p] + P.nx[p]; k < P.po[p + 1]; k++) nfar += P.pool[k] < thr;
+            const long long ny = P.po[p + 1] - P.po[p] - P.nx[p], nnear = ny - nfar;
+            if (nfar > out[20]) out[20] = nfar;
+            if (nnear > maxnear) maxnear = (int)nnear;
+            int lev = 0;
+            for (int o = d.dp[r]; o < d.dp[r + 1]; o++) {
+                const int q = pos[d.dj[o]];
+                nd++;
+                if (q >= s) {
+                    items += P.po[q + 1] - P.po[q];
+                    if (ilev[q] + 1 > lev) lev = ilev[q] + 1;
+                } else {
+                    items++;
+                }
+            }
+            ilev[p] = lev;
+            if (lev + 1 > nlev) nlev = lev + 1;
+            if (P.islong[b]) {
+                const long long rounds = (nnear + 63) / 64;
+                out[1]++;
+                out[4 + (rounds <= 12 ? rounds : 13)]++;
+                out[18] += (P.nx[p] + nfar) % 64 == 0;
+                out[19] += nfar > 0;
+            }
+        }
+        if (!P.islong[b]) {
+            out[21] += e - s < 64;
+            if (maxnear > out[22]) out[22] = maxnear;
+            if (nd + 1 + ne > elems) elems = nd + 1 + ne;
+            const long long w = 2 * ne + 1 + items + nlev + 1;
+            if (w > words) words = w;
+        }
+    }
+    out[2] = nch;
+    out[23] = elems * 8 + words * 4;
+    out[24] = elems;
+    out[25] = words;
+    free(pos);
+    free(ilev);
+    blk_free(&P, &d, ord);
+    return 0;
+}
 
 int oracle_dag_levels(int kind, int n, const int *rp, const int *ci) {
     if (n <= 0 || kind < 0 || kind > 1) return 0;

@@ -112,6 +112,29 @@ int oracle_trsv_blocks_f64(int kind, int n, const int *rowptr, const int *colidx
                            double alpha, const double *x, double *y, const int *params);
 int oracle_trsv_blocks_f32(int kind, int n, const int *rowptr, const int *colidx, const float *vals,
                            float alpha, const float *x, float *y, const int *params, int ftz);
+/* Facts of the block plan of that DAG under params (null: the defaults), from
+ * the restated plan alone; tests pin with them which planner rules a matrix
+ * reaches. out holds ORACLE_BLK_FACTS + n values:
+ *   [0] blocks  [1] long blocks  [2] chunks  [3] chunks started by the lcap
+ *   rule (not by length)
+ *   [4 + r] long blocks of r rounds, r = ceil(in-chunk terms / 64) = 0..12;
+ *   [17] long blocks of more than 12 rounds
+ *   [18] long blocks whose x + far terms are a multiple of 64
+ *   [19] long blocks with far terms  [20] the most far terms of any row
+ *   [21] normal blocks of < 64 rows  [22] the most in-chunk terms of a row of
+ *   a normal block
+ *   [23] the LDS need of the coefficient build in bytes at fp64,
+ *   8 * [24] + 4 * [25]: over the normal blocks, [24] = max(nd + 1 + ne) and
+ *   [25] = max(2 ne + 1 + items + nlev + 1), nd the dependencies of the block's
+ *   rows, ne its pattern entries, items the sum over those dependencies of
+ *   the dependency's pattern size if it is in the block, else 1, nlev the
+ *   block's intra-block levels
+ *   [ORACLE_BLK_FACTS + g] blocks of chunk g.
+ * A row's FAR terms are its y sources before max(chunk start, block start -
+ * nw), its in-chunk terms the others. Returns 0 (< 0: bad arguments). */
+#define ORACLE_BLK_FACTS 32
+int oracle_trsv_blocks_facts(int kind, int n, const int *rowptr, const int *colidx, const int *params,
+                             long long *out);
 
 /* U y = alpha x (upper incl. diagonal) — the desc_U extension. */
 void oracle_trsv_upper_f64(int n, const int *rowptr, const int *colidx, const double *vals,

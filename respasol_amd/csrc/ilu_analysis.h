@@ -104,7 +104,6 @@ struct BlkPlanHost {
     int n = 0, nb = 0, nlong = 0, entries = 0;
     int lds_elems = 0;  // coefficient build: LDS values (T) of the largest normal block
     int lds_words = 0;  // ... and 32-bit words of its slot data (eord, rptr, recipe items, levels)
-    long long novf = 0; // long blocks' record overflow entries
     hvec<int> order;    // position -> row
     hvec<rsp::BlkDesc> desc;
     hvec<rsp::BlkRow> rows;

@@ -27,6 +27,8 @@
 //  * pattern: x sources (p and the x sources of its in-block dependencies),
 //    then y sources (the in-block dependencies' y sources and the positions
 //    of its dependencies before the block), each ascending.
+// A plan whose largest normal block does not fit the coefficient build's LDS
+// (rsp::kBlkLdsMax, at fp64) is refused: that DAG stays level-scheduled.
 // Chunks are independent (the near rule reads positions only), so they are
 // planned in parallel; so are the blocks' coefficient recipes.
 #include <algorithm>
@@ -59,8 +61,13 @@ struct ChunkPlan {
 }  // namespace
 
 bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, BlkPlanHost &bp) {
-    const int BS = rsp::kBlkRows, YMAX = env_int("RSP_BLK_YMAX", rsp::kBlkYMax), NMAX = env_int("RSP_BLK_NMAX", rsp::kBlkNear),
-              NW = env_int("RSP_BLK_NW", rsp::kBlkNearWin), CH = env_int("RSP_BLK_CH", rsp::kBlkWin);
+    // knobs (tests): only values the kernels can honour. A record has
+    // kBlkNear slots per lane, the chunk's window kBlkWin cells (16-bit slot
+    // numbers); the near window is the whole chunk (a y term of the chunk
+    // that counted as far would be read before the chunk's walk wrote it).
+    const int BS = rsp::kBlkRows, YMAX = env_int("RSP_BLK_YMAX", rsp::kBlkYMax), NW = rsp::kBlkNearWin,
+              NMAX = std::min(std::max(env_int("RSP_BLK_NMAX", rsp::kBlkNear), 0), rsp::kBlkNear),
+              CH = std::min(std::max(env_int("RSP_BLK_CH", rsp::kBlkWin), 1), rsp::kBlkWin);
     const auto t0 = std::chrono::steady_clock::now();
     auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     const int n = hp.n;
@@ -280,16 +287,11 @@ bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, 
         }
     });
     std::vector<long long> roff((size_t)nb + 1, 0);
-    long long dsum = 0, lsum = 0, osum = 0;
+    long long dsum = 0, lsum = 0;
     for (int q = 0; q < nb; q++) {
         rsp::BlkDesc &d = bp.desc[(size_t)q];
         d.doff = (int)dsum;
         d.loff = (int)lsum;
-        d.ovf = 0;
-        if (d.kind && d.kn > rsp::kBlkNear) {  // record overflow: rounds past kBlkNear
-            d.ovf = (int)osum;
-            osum += 64LL * (d.kn - rsp::kBlkNear);
-        }
         dsum += ndep[(size_t)q];
         lsum += d.nlev + 1;
         roff[(size_t)q + 1] = roff[(size_t)q] + nitem[(size_t)q];
@@ -302,8 +304,15 @@ bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, 
             bp.lds_words = std::max(bp.lds_words, (int)w);
         }
     }
-    if (dsum >= INT_MAX || roff[(size_t)nb] >= INT_MAX || lsum >= INT_MAX || osum >= INT_MAX) return false;
-    bp.novf = osum;
+    if (dsum >= INT_MAX || roff[(size_t)nb] >= INT_MAX || lsum >= INT_MAX) return false;
+    // the coefficient build stages its largest normal block in LDS (the two
+    // maxima apart, as the launch sizes them; fp64, one plan serves both
+    // types): a plan that needs more than a CU has cannot launch, so this DAG
+    // is level-scheduled instead
+    if ((long long)bp.lds_elems * 8 + (long long)bp.lds_words * 4 > rsp::kBlkLdsMax) {
+        bp = BlkPlanHost();
+        return false;
+    }
     bp.vpos.resize((size_t)std::max<long long>(dsum, 1));
     bp.eord.resize((size_t)E);
     bp.rptr.resize((size_t)E + 1);
@@ -391,10 +400,11 @@ bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, 
                 kind, prev, (double)prev / n, bprev, nb);
         fprintf(stderr,
                 "plan_blocks kind=%d n=%d levels=%d blocks=%d long=%d segments=%d entries=%d x/row=%.2f "
-                "far/row=%.2f near/row=%.2f kn/block=%.2f lds_elems=%d deps=%zu recipes=%zu %.1f ms "
-                "(greedy %.1f, rows %.1f)\n",
+                "far/row=%.2f near/row=%.2f kn/block=%.2f lds_elems=%d lds_words=%d deps=%zu recipes=%zu "
+                "%.1f ms (greedy %.1f, rows %.1f)\n",
                 kind, n, nlev, nb, nlong, (int)bp.segs.size(), E, (double)x / n, (double)far / n, (double)near / n,
-                (double)kn / std::max(nb, 1), bp.lds_elems, bp.vpos.size(), bp.rit.size(), ms(), t_greedy, t_rows);
+                (double)kn / std::max(nb, 1), bp.lds_elems, bp.lds_words, bp.vpos.size(), bp.rit.size(), ms(),
+                t_greedy, t_rows);
     }
     return true;
 }

@@ -424,11 +424,14 @@ struct IluArgs {
 constexpr int kBlkRows = 64, kBlkYMax = 32, kBlkNear = 12, kBlkNearWin = 1 << 30, kBlkWin = 16384;
 constexpr int kBlkLongCap = 64 * kBlkNear;  // a long row's in-chunk terms (one record); more start a chunk
 constexpr int kBlkPre = 6;  // records in flight in the chunk walk (trsv_blk_seg)
+// The coefficient build's dynamic LDS (a normal block staged whole): the LDS of
+// a CU. The planner refuses a plan that needs more at fp64 (that DAG is then
+// level-scheduled), the launch raises the kernel's limit to it.
+constexpr int kBlkLdsMax = 160 * 1024;
 struct alignas(16) BlkDesc {
     int p0, np, kind, kn;     // first position, rows, 0 normal / 1 long, in-chunk terms (rounds: long)
     int eoff, ne, doff, nd;   // its pattern entries (and coefficient slots), its dependencies
-    int loff, nlev, ovf, pad; // coefficient build: level ranges at lptr[loff ..], intra-block levels;
-                              // ovf: a long block's record overflow offset
+    int loff, nlev, pad[2];   // coefficient build: level ranges at lptr[loff ..], intra-block levels
 };
 struct alignas(16) BlkRow {
     int off, nx, ny, nfar;    // pattern entries [off, off + nx + ny): x, far y, near y

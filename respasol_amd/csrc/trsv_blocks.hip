@@ -316,7 +316,7 @@ hipError_t blocks_run(const BlkArgs &a, hipStream_t s) {
         static bool set = false;  // per instantiation
         if (!set) {
             const hipError_t e = hipFuncSetAttribute((const void *)trsv_blk_coef<T>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, rsp::kBlkLdsMax);
             if (e != hipSuccess) return e;
             set = true;
         }

@@ -50,6 +50,8 @@ def _load():
     lib.oracle_trsv_blocks_f64.restype = C.c_int
     lib.oracle_trsv_blocks_f32.argtypes = [C.c_int, C.c_int, ip, ip, vp, C.c_float, vp, vp, vp, C.c_int]
     lib.oracle_trsv_blocks_f32.restype = C.c_int
+    lib.oracle_trsv_blocks_facts.argtypes = [C.c_int, C.c_int, ip, ip, vp, vp]
+    lib.oracle_trsv_blocks_facts.restype = C.c_int
     lib.oracle_dlarnv.argtypes = [C.c_int, ip, C.c_int, vp]
     lib.oracle_dlarnv.restype = C.c_int
     return lib
@@ -127,18 +129,65 @@ def dag_levels(kind, rowptr, colidx):
                                  ci.ctypes.data_as(C.POINTER(C.c_int)))
 
 
+BLK_DEFAULTS = (64, 32, 12, 1 << 30, 16384, 768)  # bs, ymax, near, nw, ch, lcap (rsp_oracle.c BLK_DEFAULTS)
+BLK_LDS_MAX = 160 * 1024  # the LDS of a CU: the coefficient build's limit (rsp::kBlkLdsMax)
+BLK_FACTS = 32  # ORACLE_BLK_FACTS
+
+
+def blk_params_env(environ=None):
+    """The oracle's params for the planner knobs the environment (or the
+    mapping given) sets: RSP_BLK_YMAX, RSP_BLK_NMAX, RSP_BLK_CH, as
+    plan_blocks reads them (NMAX within [0, 12], CH within [1, 16384]); bs, nw
+    and lcap are not knobs."""
+    environ = os.environ if environ is None else environ
+
+    def env(name, dflt):
+        v = str(environ.get(name, ""))
+        return int(v) if v.strip() else dflt
+    bs, ymax, near, nw, ch, lcap = BLK_DEFAULTS
+    return (bs, env("RSP_BLK_YMAX", ymax), min(max(env("RSP_BLK_NMAX", near), 0), near), nw,
+            min(max(env("RSP_BLK_CH", ch), 1), ch), lcap)
+
+
+def _params(params):
+    return None if params is None else np.ascontiguousarray(params, np.int32)
+
+
+def blocks_facts(kind, rowptr, colidx, params=None):
+    """Facts of the oracle's block plan of the L (kind 0) or L^T (kind 1) DAG
+    (oracle_trsv_blocks_facts, rsp_oracle.h), by name."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    n = rp.shape[0] - 1
+    out = np.zeros(BLK_FACTS + max(n, 0), np.int64)
+    prm = _params(params)
+    r = lib.oracle_trsv_blocks_facts(kind, n, rp.ctypes.data_as(C.POINTER(C.c_int)),
+                                     ci.ctypes.data_as(C.POINTER(C.c_int)),
+                                     None if prm is None else prm.ctypes.data, out.ctypes.data)
+    if r < 0:
+        raise ValueError("oracle_trsv_blocks_facts: bad arguments")
+    o = [int(v) for v in out]
+    rounds = {r: o[4 + r] for r in range(13) if o[4 + r]}
+    return dict(blocks=o[0], long=o[1], chunks=o[2], cap_cuts=o[3], rounds=rounds, rounds_over_12=o[17],
+                long_aligned=o[18], long_far=o[19], max_far=o[20], partial=o[21], max_near=o[22],
+                lds=o[23], lds_elems=o[24], lds_words=o[25], per_chunk=o[BLK_FACTS:BLK_FACTS + o[2]])
+
+
 def blocks_wanted(kind, rowptr, colidx):
     """The product's rule for a block-inverse solve of that DAG
-    (rsp_an::blocks_wanted, ilu_blocks.cpp): RSP_ILU_BLOCKS -1 (default) for
-    DAGs of <= 32 rows per level on average, 1 always, 0 never."""
+    (rsp_an::blocks_wanted and plan_blocks, ilu_blocks.cpp): RSP_ILU_BLOCKS -1
+    (default) for DAGs of <= 32 rows per level on average, 1 always, 0 never;
+    and never where the plan's coefficient build needs more LDS than a CU has."""
     mode = int(os.environ.get("RSP_ILU_BLOCKS", "-1") or "-1")
     n = len(rowptr) - 1
     if mode == 0 or n <= 0:
         return False
-    return mode > 0 or n <= 32 * dag_levels(kind, rowptr, colidx)
+    if mode < 0 and n > 32 * dag_levels(kind, rowptr, colidx):
+        return False
+    return blocks_facts(kind, rowptr, colidx, blk_params_env())["lds"] <= BLK_LDS_MAX
 
 
-def trsv(kind, rowptr, colidx, vals, x, alpha=1.0, ftz=False):
+def trsv(kind, rowptr, colidx, vals, x, alpha=1.0, ftz=False, params=None, count=False):
     """kind in {'lower_n', 'lower_t', 'upper', 'lower_n_ref', 'lower_t_ref',
     'lower_n_split', 'lower_t_split', 'lower_n_blocks', 'lower_t_blocks'}.
     '*_ref' is the reference's own order (L: column ascending; L^T: the
@@ -148,10 +197,14 @@ def trsv(kind, rowptr, colidx, vals, x, alpha=1.0, ftz=False):
     'lower_n' / 'lower_t' follow the product's plan order: the block order
     where the product plans blocks for that DAG (blocks_wanted), else the
     reference's, or the split one where RSP_ILU_SPLIT=1 is set (the analysis
-    knobs)."""
+    knobs). params: the block order's {bs, ymax, near, nw, ch, lcap} (None:
+    the defaults; 'lower_n' / 'lower_t' take the environment's knobs,
+    blk_params_env(), as the product's planner does). count=True (block
+    orders only): returns (y, the plan's blocks)."""
     split = os.environ.get("RSP_ILU_SPLIT", "0") not in ("", "0")
     if kind in ("lower_n", "lower_t") and blocks_wanted(0 if kind == "lower_n" else 1, rowptr, colidx):
         kind += "_blocks"
+        params = blk_params_env() if params is None else params
     kind = {"lower_n": "lower_n_split" if split else "lower_n",
             "lower_t": "lower_t_split" if split else "lower_t",
             "lower_n_ref": "lower_n", "lower_t_ref": "lower_t"}.get(kind, kind)
@@ -163,17 +216,19 @@ def trsv(kind, rowptr, colidx, vals, x, alpha=1.0, ftz=False):
     y = np.empty(n, v.dtype)
     if kind.endswith("_blocks"):
         bk = 0 if kind == "lower_n_blocks" else 1
+        prm = _params(params)
+        pp = None if prm is None else prm.ctypes.data
         if v.dtype == np.float64:
             r = lib.oracle_trsv_blocks_f64(bk, n, rp.ctypes.data_as(C.POINTER(C.c_int)),
                                            ci.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data, alpha,
-                                           xx.ctypes.data, y.ctypes.data, None)
+                                           xx.ctypes.data, y.ctypes.data, pp)
         else:
             r = lib.oracle_trsv_blocks_f32(bk, n, rp.ctypes.data_as(C.POINTER(C.c_int)),
                                            ci.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data, alpha,
-                                           xx.ctypes.data, y.ctypes.data, None, 1 if ftz else 0)
+                                           xx.ctypes.data, y.ctypes.data, pp, 1 if ftz else 0)
         if r < 0:
             raise ValueError("oracle_trsv_blocks: bad arguments")
-        return y
+        return (y, r) if count else y
     if v.dtype == np.float64:
         getattr(lib, f"oracle_trsv_{kind}_f64")(n, rp.ctypes.data_as(C.POINTER(C.c_int)),
                                                 ci.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data,

@@ -51,9 +51,10 @@ def solve_both(handle, A, dtype, x, ftz=False, alpha=1.0):
 
 
 def check(A, rv, x, z, y, dtype, ftz=False, alpha=1.0):
+    """Returns the oracle's block counts (L, L^T)."""
     xx = np.ascontiguousarray(x, NP[dtype])
-    rz = ob.trsv("lower_n_blocks", A.rowptr, A.colidx, rv, xx, alpha=alpha, ftz=ftz)
-    ry = ob.trsv("lower_t_blocks", A.rowptr, A.colidx, rv, rz, alpha=alpha, ftz=ftz)
+    rz, bl = ob.trsv("lower_n_blocks", A.rowptr, A.colidx, rv, xx, alpha=alpha, ftz=ftz, count=True)
+    ry, bt = ob.trsv("lower_t_blocks", A.rowptr, A.colidx, rv, rz, alpha=alpha, ftz=ftz, count=True)
     # the reference's order, for the tolerance
     fz = ob.trsv("lower_n_ref", A.rowptr, A.colidx, rv, xx, alpha=alpha, ftz=ftz).astype(np.float64)
     fy = ob.trsv("lower_t_ref", A.rowptr, A.colidx, rv, z, alpha=alpha, ftz=ftz).astype(np.float64)
@@ -62,6 +63,8 @@ def check(A, rv, x, z, y, dtype, ftz=False, alpha=1.0):
     assert np.linalg.norm(y.astype(np.float64) - fy) <= tol * max(np.linalg.norm(fy), 1e-300)
     assert np.array_equal(z, rz), f"L solve: {np.count_nonzero(z != rz)} of {z.size} differ"
     assert np.array_equal(y, ry), f"L^T solve: {np.count_nonzero(y != ry)} of {y.size} differ"
+    assert bl > 0 and bt > 0
+    return bl, bt
 
 
 @pytest.mark.parametrize("dtype,ftz", [(torch.float64, False), (torch.float32, False), (torch.float32, True)])
@@ -72,10 +75,8 @@ def test_deep_circuits_full_size(handle, name, dtype, ftz):
     A = csr.surrogate(name)
     x, _ = csr.dlarnv(2, [0, 0, 0, 1], A.n)
     il, rv, z, y = solve_both(handle, A, dtype, x, ftz)
-    bl, bt = il.solve_blocks()
-    assert bl > 0 and bt > 0
     assert ob.blocks_wanted(0, A.rowptr, A.colidx) and ob.blocks_wanted(1, A.rowptr, A.colidx)
-    check(A, rv, x, z, y, dtype, ftz)
+    assert il.solve_blocks() == check(A, rv, x, z, y, dtype, ftz)
 
 
 @pytest.mark.parametrize("name,scale", [("xenon2", 0.05), ("offshore", 0.05), ("ss1", 0.1), ("cfd2", 0.05),
@@ -89,8 +90,7 @@ def test_forced_on_other_families(handle, monkeypatch, name, scale):
     x, _ = csr.dlarnv(2, [1, 2, 3, 5], A.n)
     for dtype in (torch.float64, torch.float32):
         il, rv, z, y = solve_both(handle, A, dtype, x, alpha=-0.75)
-        assert min(il.solve_blocks()) > 0
-        check(A, rv, x, z, y, dtype, alpha=-0.75)
+        assert il.solve_blocks() == check(A, rv, x, z, y, dtype, alpha=-0.75)
 
 
 @pytest.mark.parametrize("fixture", ["bcspwr01.mtx", "one.mtx", "random_300.mtx", "empty_rows.mtx"])
@@ -102,8 +102,8 @@ def test_small_fixtures(handle, monkeypatch, fixture):
     if sz >= 0:
         pytest.skip("structural zero: no factor")
     x = np.linspace(-1.0, 2.0, A.n)
-    _, rv, z, y = solve_both(handle, A, torch.float64, x)
-    check(A, rv, x, z, y, torch.float64)
+    il, rv, z, y = solve_both(handle, A, torch.float64, x)
+    assert il.solve_blocks() == check(A, rv, x, z, y, torch.float64)
 
 
 def test_level_path_still_selectable(handle, monkeypatch):
@@ -136,10 +136,10 @@ def test_default_plan_deep_dag_true_lu(handle, dtype, alpha):
     z = il.solve_lower(va, torch.from_numpy(xx).cuda(), alpha=alpha)
     y = il.solve_upper(va, z, alpha=alpha)
     assert il.solve_zero_pivot(il.TRSV_L) == -1 and il.solve_zero_pivot(il.TRSV_U) == -1
-    assert il.solve_blocks()[0] > 0
     rv, sz, zp = ob.ilu0(A.rowptr, A.colidx, A.values.astype(NP[dtype]))
     assert sz == -1 and zp == -1 and np.array_equal(va.cpu().numpy(), rv)
-    rz = ob.trsv("lower_n_blocks", A.rowptr, A.colidx, rv, xx, alpha=alpha)
+    rz, bl = ob.trsv("lower_n_blocks", A.rowptr, A.colidx, rv, xx, alpha=alpha, count=True)
+    assert bl > 0 and il.solve_blocks()[0] == bl
     assert np.array_equal(z.cpu().numpy(), rz), f"L solve: {np.count_nonzero(z.cpu().numpy() != rz)} differ"
     ry = ob.trsv("upper", A.rowptr, A.colidx, rv, rz, alpha=alpha)
     assert np.array_equal(y.cpu().numpy(), ry), f"U solve: {np.count_nonzero(y.cpu().numpy() != ry)} differ"
