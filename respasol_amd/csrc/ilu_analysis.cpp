@@ -1675,28 +1675,6 @@ rsp_status_t plan_host(int n, const int *rp, const int *ci, long long slot_cap, 
     return RSP_STATUS_SUCCESS;
 }
 
-namespace {
-struct Fnv {  // FNV-1a over 8-byte words (bytes for the tail)
-    uint64_t h = 1469598103934665603ULL;
-    void bytes(const void *p, size_t n) {
-        const unsigned char *c = (const unsigned char *)p;
-        size_t i = 0;
-        for (; i + 8 <= n; i += 8) {
-            uint64_t w;
-            memcpy(&w, c + i, 8);
-            h = (h ^ w) * 1099511628211ULL;
-        }
-        for (; i < n; i++) h = (h ^ c[i]) * 1099511628211ULL;
-    }
-    template <typename V>
-    void vec(const hvec<V> &v) {
-        const uint64_t n = v.size();
-        bytes(&n, sizeof(n));
-        if (!v.empty()) bytes(v.data(), v.size() * sizeof(V));
-    }
-};
-}  // namespace
-
 uint64_t digest(const IluHostPlan &hp) {
     Fnv f;
     f.bytes(&hp.n, sizeof(hp.n));

@@ -11,6 +11,7 @@
 
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <exception>
 #include <functional>
@@ -216,11 +217,32 @@ bool blocks_wanted(int n, int nlev);
 bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, BlkPlanHost &bp);
 // Build the U DAG's levels and solve plan (lazily, on first use).
 void plan_u(const int *rp, const int *ci, IluHostPlan &hp);
+// FNV-1a over 8-byte words (bytes for the tail): the plan digests (digest
+// below, rsp_plan::digest)
+struct Fnv {
+    uint64_t h = 1469598103934665603ULL;
+    void bytes(const void *p, size_t n) {
+        const unsigned char *c = (const unsigned char *)p;
+        size_t i = 0;
+        for (; i + 8 <= n; i += 8) {
+            uint64_t w;
+            memcpy(&w, c + i, 8);
+            h = (h ^ w) * 1099511628211ULL;
+        }
+        for (; i < n; i++) h = (h ^ c[i]) * 1099511628211ULL;
+    }
+    template <typename V>
+    void vec(const hvec<V> &v) {
+        const uint64_t n = v.size();
+        bytes(&n, sizeof(n));
+        if (!v.empty()) bytes(v.data(), v.size() * sizeof(V));
+    }
+};
 // 64-bit digest (FNV-1a) of every array of the plan (tests: identical plans).
 uint64_t digest(const IluHostPlan &hp);
 
 // f(lo, hi) over [0, n) in contiguous blocks of >= grain on the analysis'
-// worker pool (also used by the SpMV planner, rsp_api.cpp make_tile_plan)
+// worker pool (also used by the SpMV planner, spmv_plan.cpp)
 void parallel_for(long long n, long long grain, const std::function<void(long long, long long)> &f);
 
 }  // namespace rsp_an

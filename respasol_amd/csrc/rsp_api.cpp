@@ -1,13 +1,12 @@
 // rsp_api.cpp — the handle, the matrix descriptor and SpMV of include/rsp.h
-// (the C-ABI operator library librsp.so): the host-side row-block schedule
-// (make_tile_plan), the launches of the kernels in spmv.hip, the batch,
-// gather / scatter. Mirrors the cuSPARSE lifecycle the reference driver uses
-// (GPU/spmv.cu:122-186); see include/rsp.h for the per-call mapping. ILU(0)
-// and the Krylov solvers: api_ilu_analysis.cpp, api_ilu_solve.cpp,
-// api_krylov.cpp (rsp_internal.h).
+// (the C-ABI operator library librsp.so): the upload of the host-side
+// row-block schedule (spmv_plan.h), the launches of the kernels in spmv.hip,
+// the batch, gather / scatter. Mirrors the cuSPARSE lifecycle the reference
+// driver uses (GPU/spmv.cu:122-186); see include/rsp.h for the per-call
+// mapping. ILU(0) and the Krylov solvers: api_ilu_analysis.cpp,
+// api_ilu_solve.cpp, api_krylov.cpp (rsp_internal.h).
 
 #include "rsp_internal.h"
-#include "spmv_pack.h"
 
 #include <atomic>
 
@@ -15,7 +14,8 @@ using namespace rsp_api;
 
 using rsp::SpmvBlock;
 using rsp::SpmvLongRow;
-using rsp::SpmvTile;
+using rsp_plan::PlanOptions;
+using rsp_plan::TilePlan;
 
 namespace {
 std::atomic<unsigned long long> g_plan_next{1};
@@ -24,369 +24,24 @@ unsigned long long plan_new_gen() { return g_plan_next.fetch_add(1); }
 
 /* ----------------------------------------------------------------- SpMV */
 
-struct SpmvBounds {
-    size_t nblocks, nlong, nslots;
-};
-
-static SpmvBounds spmv_bounds(int64_t rows, int64_t nnz, int cap) {
-    // greedy packing: two consecutive size-closed tiles exceed `cap`, long
-    // rows contribute <= nnz/cap + 1 chunks each side.
-    // + every row longer than kSpmvLongRow may sit in a tile of its own and
-    // close the tile before it: <= 2 * nnz / kSpmvLongRow extra tiles.
-    SpmvBounds b;
-    size_t q = (size_t)(nnz / cap) + 1;
-    size_t l = (size_t)(nnz / rsp::kSpmvLongRow) + 1;
-    b.nlong = q;
-    b.nslots = 2 * q + 1;
-    b.nblocks = 6 * q + 2 * l + (size_t)(rows / rsp::kSpmvMaxRows) + 8;
-    b.nblocks += std::min<size_t>(b.nblocks, 8192);  // headroom for spread-out small plans
-    return b;
+static int64_t spmv_resident_tiles(rsp_handle_t h, rsp_datatype_t t) {
+    return (int64_t)rsp_k::spmv_tiles_per_cu((int)elem_size(t)) * h->num_cus;
 }
 
-// Workspace: [tiles | long rows | chunk partials | per-tile column base |
-// per-tile packed-record offset | 16-bit column offsets (2 B per stored
-// entry) | staged tiles' runs, then their packed records].
-struct SpmvLayout {
-    size_t off_long, off_part, off_cbase, off_poff, off_cidx, off_runs, bytes;
-};
-static SpmvLayout spmv_layout(const SpmvBounds &b, size_t elem, int64_t nnz, size_t run_ints = 0) {
-    SpmvLayout l;
-    l.off_long = align256(b.nblocks * sizeof(SpmvBlock));
-    l.off_part = l.off_long + align256(b.nlong * sizeof(SpmvLongRow));
-    l.off_cbase = l.off_part + align256(b.nslots * 2 * elem);  // value + ticket per slot
-    l.off_poff = l.off_cbase + align256(b.nblocks * sizeof(int));
-    l.off_cidx = l.off_poff + align256(b.nblocks * sizeof(int));
-    l.off_runs = l.off_cidx + align256((size_t)std::max<int64_t>(nnz, 0) * sizeof(uint16_t));
-    l.bytes = l.off_runs + align256(run_ints * sizeof(int));
-    return l;
-}
-
-static int tile_cap(rsp_datatype_t t) {
-    return t == RSP_R_64F ? SpmvTile<double>::kMaxNnz : SpmvTile<float>::kMaxNnz;
-}
-static int chunk_cap(rsp_datatype_t t) {
-    return t == RSP_R_64F ? SpmvTile<double>::kChunk : SpmvTile<float>::kChunk;
-}
-// Tile row cuts: RSP_SPMV_VARIANT bit 6 aligns them to 128-B y lines, bit 7
-// to 64 B (tuning knob; default unaligned).
-static int spmv_row_align(rsp_handle_t h, rsp_datatype_t t) {
-    const int e = (int)elem_size(t);
-    return (h->spmv_variant & 64) ? 128 / e : (h->spmv_variant & 128) ? 64 / e : 1;
-}
-
-// Greedy row-block schedule over host row offsets (see spmv.hip header).
-// Rows longer than kSpmvLongRow get tiles of their own (one per `chunk`
-// entries); the others are packed into tiles of <= cap entries / maxrows rows.
-static int build_spmv_plan(const int *rp, int m, int cap, int chunk, rsp_an::hvec<SpmvBlock> &blocks,
-                           rsp_an::hvec<SpmvLongRow> &longrows, int *nslots,
-                           int maxrows = rsp::kSpmvMaxRows, int row_align = 1) {
-    blocks.clear();
-    longrows.clear();
-    int slots = 0;
-    int r = 0;
-    while (r < m) {
-        int len = rp[r + 1] - rp[r];
-        if (len > rsp::kSpmvLongRow) {
-            if (len <= chunk) {  // one chunk: reduced and written in place
-                SpmvBlock b;
-                b.r0 = r;
-                b.r1 = rsp::kSpmvWholeRow;
-                b.k0 = rp[r];
-                b.k1 = rp[r + 1];
-                blocks.push_back(b);
-                r++;
-                continue;
-            }
-            SpmvLongRow lr;
-            lr.row = r;
-            lr.first = slots;
-            lr.nchunks = 0;
-            lr.pad = 0;
-            for (int k = rp[r]; k < rp[r + 1]; k += chunk) {
-                SpmvBlock b;
-                b.r0 = r;
-                b.r1 = -(slots + 1);
-                b.k0 = k;
-                b.k1 = std::min(k + chunk, rp[r + 1]);
-                blocks.push_back(b);
-                slots++;
-                lr.nchunks++;
-            }
-            longrows.push_back(lr);
-            r++;
-            continue;
-        }
-        int start = r, nnz = 0;
-        while (r < m && r - start < maxrows) {
-            int l = rp[r + 1] - rp[r];
-            // a tile always takes its first row (<= kSpmvLongRow <= kMaxNnz)
-            if (l > rsp::kSpmvLongRow || (r > start && nnz + l > cap)) break;
-            nnz += l;
-            r++;
-        }
-        // row_align > 1: end a packed tile on a multiple of row_align rows,
-        // so its y stores cover whole lines, where the tile keeps >= 3/4 of
-        // its entries
-        if (row_align > 1 && r < m && r % row_align != 0) {
-            const int ra = r - r % row_align;
-            if (ra > start && (int64_t)(rp[ra] - rp[start]) * 4 >= (int64_t)(rp[r] - rp[start]) * 3) r = ra;
-        }
-        SpmvBlock b;
-        b.r0 = start;
-        b.r1 = r;
-        b.k0 = rp[start];
-        b.k1 = rp[r];
-        blocks.push_back(b);
-    }
-    *nslots = slots;
-    return 0;
-}
-
-// A complete SpMV schedule over host row offsets `rp` and column indices `ci`:
-// tiles (interior tiles first when local_cols >= 0), long rows, per-tile
-// column base and the 16-bit column offsets.
-struct TilePlan {
-    rsp_an::hvec<SpmvBlock> blocks;
-    rsp_an::hvec<SpmvLongRow> longrows;
-    int nslots = 0, nint = 0;
-    rsp_an::hvec<int> cbase;
-    rsp_an::hvec<uint16_t> c16;
-    rsp_an::hvec<int> runs;  // staged tiles' run descriptors (int pairs), then the packed records; SpmvArgs::runs
-    rsp_an::hvec<int> poff;  // per tile: packed record (SpmvArgs::poffs), -1 = none
-    int64_t nnz_c16 = 0;     // entries not read through the int32 colidx (16-bit offsets, slot indices, packed slots)
-    int64_t nnz_staged = 0;  // ... of which in staged tiles
-    int64_t tiles_packed = 0, nnz_packed = 0;  // ... of which in packed tiles
-};
-
-// RSP_SPMV_PACK (plan time): 0 no packed records (the unpacked plan), 1 the
-// slot fields only, 2 (default) slot fields and row offsets. On the big set's
-// batched fp64 launch: 534.8 / 530.7 / 518.8 us (profiles/r07_pack_ab.txt).
-static int spmv_pack_mode() { return std::min(std::max(env_int("RSP_SPMV_PACK", 2), 0), 2); }
-
-// Packed records (spmv_pack.h) of the staged tiles whose slot fields are
-// strictly fewer bytes than their 16-bit words, appended to p.runs after every
-// run descriptor (whose offsets have the smaller range), each 16-B aligned.
-// An offset past the encoding's range leaves the tile unpacked.
-template <typename T>
-static void pack_staged_tiles(const int *rp, TilePlan &p, int mode) {
-    constexpr int VW = SpmvTile<T>::kVec, IT = rsp::kSpmvIter, NTH = rsp::kSpmvThreads;
-    constexpr int IW = rsp_pack::index_words(NTH, IT * VW);
-    p.poff.assign(p.blocks.size(), -1);
-    p.tiles_packed = p.nnz_packed = 0;
-    if (mode <= 0) return;
-    int64_t end = ((int64_t)p.runs.size() + 3) & ~(int64_t)3;
-    for (size_t t = 0; t < p.blocks.size(); t++) {
-        const SpmvBlock &b = p.blocks[t];
-        if (p.cbase[t] > -2 || b.r1 < 0 || !rsp_pack::eligible(NTH, IT * VW, b.k1 - b.k0)) continue;
-        const int64_t words = IW + (mode >= 2 ? rsp_pack::row_words(b.r1 - b.r0) : 0);
-        if (end + words >= (1LL << 30)) break;  // (poff = word << 1 | rows; never reached on real matrices)
-        p.poff[t] = (int)(end << 1) | (mode >= 2 ? 1 : 0);
-        end = (end + words + 3) & ~(int64_t)3;
-        p.tiles_packed++;
-        p.nnz_packed += b.k1 - b.k0;
-    }
-    if (p.tiles_packed == 0) return;
-    p.runs.resize((size_t)end + 4, 0);  // (+ 16 B: a vector load of a record's last words stays inside)
-    rsp_an::parallel_for((long long)p.blocks.size(), 64, [&](long long t0, long long t1) {
-        for (long long t = t0; t < t1; t++) {
-            if (p.poff[(size_t)t] < 0) continue;
-            const SpmvBlock &b = p.blocks[(size_t)t];
-            uint32_t *rec = reinterpret_cast<uint32_t *>(p.runs.data()) + (p.poff[(size_t)t] >> 1);
-            rsp_pack::pack_slots(p.c16.data(), b.k0, b.k1, VW, IT, NTH, rec);
-            if (p.poff[(size_t)t] & 1) rsp_pack::pack_rows(rp, b.r0, b.r1 - b.r0, b.k0 & ~(VW - 1), rec + IW);
-        }
-    });
-}
-
-// spread > 0: a plan of fewer tiles than `spread` (the resident workgroup
-// slots it may use) is re-packed into up to `spread` smaller tiles, so a lone
-// launch does not leave slots idle. Long rows do not depend on the packing
-// cap (they are cut at the fixed chunk), so every spread of one matrix has
-// the same long rows and partial slots.
-static void make_tile_plan(const int *rp, const int *ci, int m, int64_t nnz_bound,
-                           rsp_datatype_t type, int64_t spread, int64_t local_cols, bool use_c16,
-                           TilePlan &p, int row_align = 1, bool use_stage = true) {
-    const int chunk = chunk_cap(type);
-    const int cap = tile_cap(type);
-    const int align = row_align;
-    const int maxrows = type == RSP_R_64F ? SpmvTile<double>::kMaxRows : SpmvTile<float>::kMaxRows;
-    build_spmv_plan(rp, m, cap, chunk, p.blocks, p.longrows, &p.nslots, maxrows, align);
-    const int64_t nb = (int64_t)p.blocks.size();
-    if (spread > 0 && nb > 0 && nb < spread) {
-        const SpmvBounds bb = spmv_bounds(m, std::max<int64_t>(nnz_bound, 0), chunk);
-        const int64_t nnz_s = rp[(size_t)m];
-        int c = (int)std::max<int64_t>(64, std::min<int64_t>(cap, (nnz_s + spread - 1) / spread));
-        for (int tries = 0; tries < 32 && c < cap; tries++) {
-            rsp_an::hvec<SpmvBlock> b2;
-            rsp_an::hvec<SpmvLongRow> l2;
-            int s2 = 0;
-            build_spmv_plan(rp, m, c, chunk, b2, l2, &s2, maxrows, align);
-            if ((int64_t)b2.size() <= spread && b2.size() <= bb.nblocks) {
-                p.blocks.swap(b2);
-                p.longrows.swap(l2);
-                p.nslots = s2;
-                break;
-            }
-            c += std::max(8, c / 16);
-        }
-    }
-    // Random-band matrices (round 4): tiles whose columns lie in a band
-    // narrower than 65536 but scattered over it (more runs than a staged
-    // tile's run table holds) are staged by an explicit column LIST instead
-    // (below); that needs at most kStageSlots distinct columns per tile, so
-    // such a matrix is re-packed with tiles of at most kStageSlots entries
-    // (the canonical summation order does not depend on the packing). Judged
-    // on a sample of 64 tiles; not for spread plans (already small tiles).
-    const int ucap = type == RSP_R_64F ? SpmvTile<double>::kStageSlots : SpmvTile<float>::kStageSlots;
-    const bool list_ok = use_stage && use_c16 && type == RSP_R_64F && SpmvTile<double>::kStageList &&
-                         env_int("RSP_SPMV_STAGE_LIST", 1) != 0;
-    if (list_ok && (int64_t)p.blocks.size() == nb && nb > 0) {
-        int64_t band = 0, all = 0;
-        std::vector<int> cols;
-        const size_t step = std::max<size_t>(1, p.blocks.size() / 64);
-        for (size_t t = 0; t < p.blocks.size(); t += step) {
-            const SpmvBlock &bk = p.blocks[t];
-            if (bk.r1 < 0 || bk.k1 <= bk.k0) continue;
-            cols.assign(ci + bk.k0, ci + bk.k1);
-            std::sort(cols.begin(), cols.end());
-            cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-            int R = 1;
-            for (size_t u = 1; u < cols.size(); u++) R += cols[u] != cols[u - 1] + 1;
-            all += bk.k1 - bk.k0;
-            if (cols.back() - cols.front() <= 65535 && R > rsp::kStageRuns && (int)cols.size() > ucap)
-                band += bk.k1 - bk.k0;
-        }
-        if (2 * band > all) {
-            rsp_an::hvec<SpmvBlock> b2;
-            rsp_an::hvec<SpmvLongRow> l2;
-            int s2 = 0;
-            // RSP_SPMV_LIST_CAP (A/B knob): a smaller tile for the re-packed plan
-            const int lcap = std::min(std::max(env_int("RSP_SPMV_LIST_CAP", ucap), 64), ucap);
-            build_spmv_plan(rp, m, std::min(cap, lcap), chunk, b2, l2, &s2, maxrows, align);
-            p.blocks.swap(b2);
-            p.longrows.swap(l2);
-            p.nslots = s2;
-        }
-    }
-    // split schedule (rsp_spmat_set_local_cols): tiles reading own columns
-    // only first; long-row tiles always in the second part (with the fixup)
-    p.nint = 0;
-    if (local_cols >= 0) {
-        auto interior = [&](const SpmvBlock &b) {
-            if (b.r1 < 0) return false;
-            for (int k = b.k0; k < b.k1; k++)
-                if (ci[(size_t)k] >= local_cols) return false;
-            return true;
-        };
-        auto mid = std::stable_partition(p.blocks.begin(), p.blocks.end(), interior);
-        p.nint = (int)(mid - p.blocks.begin());
-    }
-    // 16-bit column offsets: a tile whose columns span < 65536 reads
-    // col = cbase + off (2 B per entry instead of 4; the int32 colidx is not
-    // read for it). Staged tiles (round 4, spmv.hip stream_products_staged):
-    // where the tile's distinct columns are few (at most kStageSlots, at most
-    // RSP_SPMV_STAGE_PCT % of its entries, default 80) in at most kStageRuns
-    // contiguous runs, its 16-bit values are instead the entries' slots in the
-    // sorted list of those columns, and the runs ({first column, first slot},
-    // then {0, slots}) go to `runs`. Tiles are planned in parallel.
-    const int64_t nnz_s = m > 0 ? rp[(size_t)m] : 0;
-    p.cbase.assign(p.blocks.size(), -1);
-    p.c16.clear();
-    p.runs.clear();
-    p.poff.assign(p.blocks.size(), -1);
-    p.tiles_packed = p.nnz_packed = 0;
-    p.nnz_c16 = 0;
-    p.nnz_staged = 0;
-    if (use_c16 && nnz_s > 0 && nnz_s <= nnz_bound) {
-        p.c16.assign((size_t)nnz_s, 0);
-        const long long nt = (long long)p.blocks.size();
-        const long long pct = std::min(std::max(env_int("RSP_SPMV_STAGE_PCT", 80), 0), 100);
-        const int64_t xelem = type == RSP_R_64F ? 8 : 4;
-        std::vector<std::vector<int>> truns(use_stage ? (size_t)nt : 0);
-        std::vector<char> tmode(use_stage ? (size_t)nt : 0, 0);  // 1 runs, 2 list
-        std::atomic<int64_t> n16{0}, nst{0};
-        rsp_an::parallel_for(nt, 64, [&](long long t0, long long t1) {
-            std::vector<int> cols;
-            int64_t c16n = 0, stn = 0;
-            for (long long t = t0; t < t1; t++) {
-                const SpmvBlock &bk = p.blocks[(size_t)t];
-                if (bk.k1 <= bk.k0) continue;
-                int lo = ci[(size_t)bk.k0], hi = lo;
-                for (int k = bk.k0 + 1; k < bk.k1; k++) {
-                    lo = std::min(lo, ci[(size_t)k]);
-                    hi = std::max(hi, ci[(size_t)k]);
-                }
-                if (hi - lo > 65535) continue;
-                const int len = bk.k1 - bk.k0;
-                c16n += len;
-                // staged x loads use 32-bit byte offsets into a buffer resource of
-                // 0x7ffffffc bytes (spmv.hip stream_products_staged): a tile whose
-                // columns reach past that keeps the plain 16-bit offsets
-                const bool x_in_rsrc = ((int64_t)hi + 1) * xelem <= (int64_t)0x7ffffffc;
-                if (use_stage && bk.r1 >= 0 && x_in_rsrc) {  // (long-row chunks keep the offsets)
-                    cols.assign(ci + bk.k0, ci + bk.k1);
-                    std::sort(cols.begin(), cols.end());
-                    cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-                    const int U = (int)cols.size();
-                    int R = 1;
-                    for (int u = 1; u < U; u++) R += cols[(size_t)u] != cols[(size_t)u - 1] + 1;
-                    const bool runs_mode = U <= ucap && R <= rsp::kStageRuns && 100LL * U <= pct * len;
-                    const bool list_mode = !runs_mode && list_ok && U <= ucap && R > rsp::kStageRuns;
-                    if (runs_mode || list_mode) {
-                        std::vector<int> &r = truns[(size_t)t];
-                        tmode[(size_t)t] = runs_mode ? 1 : 2;
-                        if (runs_mode) {
-                            r.reserve(2 * (size_t)(R + 1));
-                            for (int u = 0; u < U; u++)
-                                if (u == 0 || cols[(size_t)u] != cols[(size_t)u - 1] + 1) {
-                                    r.push_back(cols[(size_t)u]);
-                                    r.push_back(u);
-                                }
-                            r.push_back(0);
-                            r.push_back(U);
-                        } else {  // {base column, U}, then the U column offsets as uint16, padded to 8 B
-                            r.assign(2 + 2 * (size_t)((U + 3) / 4), 0);
-                            r[0] = cols[0];
-                            r[1] = U;
-                            uint16_t *o = reinterpret_cast<uint16_t *>(r.data() + 2);
-                            for (int u = 0; u < U; u++) o[u] = (uint16_t)(cols[(size_t)u] - cols[0]);
-                        }
-                        for (int k = bk.k0; k < bk.k1; k++)
-                            p.c16[(size_t)k] = (uint16_t)(std::lower_bound(cols.begin(), cols.end(), ci[(size_t)k]) -
-                                                          cols.begin());
-                        stn += len;
-                        continue;
-                    }
-                }
-                p.cbase[(size_t)t] = lo;
-                for (int k = bk.k0; k < bk.k1; k++) p.c16[(size_t)k] = (uint16_t)(ci[(size_t)k] - lo);
-            }
-            n16 += c16n;
-            nst += stn;
-        });
-        p.nnz_c16 = n16;
-        p.nnz_staged = nst;
-        if (use_stage) {  // descriptors concatenated in tile order; cbase = -2 - (pair offset << 8 | runs)
-            for (size_t t = 0; t < truns.size(); t++) {
-                const std::vector<int> &r = truns[t];
-                if (r.empty()) continue;
-                const int64_t off = (int64_t)p.runs.size() / 2;
-                // runs mode: descriptors + sentinel; list mode: 255 (header {base, U} + offsets)
-                const int nr = tmode[t] == 2 ? 255 : (int)r.size() / 2 - 1;
-                if (off >= (1LL << 22)) {  // (encoding range; never reached on real matrices)
-                    p.nnz_c16 -= p.blocks[t].k1 - p.blocks[t].k0;
-                    p.nnz_staged -= p.blocks[t].k1 - p.blocks[t].k0;
-                    continue;  // cbase stays -1: the int32 path
-                }
-                p.cbase[t] = -2 - (int)((off << 8) | nr);
-                p.runs.insert(p.runs.end(), r.begin(), r.end());
-            }
-            if (type == RSP_R_64F)
-                pack_staged_tiles<double>(rp, p, spmv_pack_mode());
-            else
-                pack_staged_tiles<float>(rp, p, spmv_pack_mode());
-        }
-    }
+// The planner's options for a matrix of `local_cols` under the handle's
+// RSP_SPMV_VARIANT (plan-time bits): bit 5 keeps every tile on the int32
+// indices, bit 6 aligns the tile row cuts to 128-B y lines, bit 7 to 64 B
+// (tuning knob; default unaligned), kSpmvVariantNoStage: no staged tiles.
+// `spread`: PlanOptions::spread.
+static PlanOptions handle_plan_options(rsp_handle_t h, rsp_datatype_t t, int64_t local_cols, int64_t spread) {
+    const int e = (int)elem_size(t), v = h->spmv_variant;
+    PlanOptions o = rsp_plan::plan_options(t);
+    o.spread = spread;
+    o.local_cols = local_cols;
+    o.row_align = (v & 64) ? 128 / e : (v & 128) ? 64 / e : 1;
+    o.use_c16 = !(v & 32);
+    o.use_stage = !(v & rsp::kSpmvVariantNoStage);
+    return o;
 }
 
 // Row offsets and column indices of `mat` on the host, validated (base 0,
@@ -422,10 +77,6 @@ static rsp_status_t download_pattern(rsp_handle_t h, rsp_spmat_t mat, rsp_an::hv
     return RSP_STATUS_SUCCESS;
 }
 
-static int64_t spmv_resident_tiles(rsp_handle_t h, rsp_datatype_t t) {
-    return (int64_t)rsp_k::spmv_tiles_per_cu((int)elem_size(t)) * h->num_cus;
-}
-
 // Build the schedule of `mat` for `compute_type` into the matrix's own device
 // memory (host-blocking; see struct rsp_spmat).
 rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t compute_type) {
@@ -440,25 +91,20 @@ rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t 
     // faster per call: dc1 8.75 -> 7.02 us, G2_circuit 8.13 -> 6.10, ASIC_320ks
     // 11.77 -> 9.22, ss1 8.49 -> 6.61, matrix-new_3 9.10 -> 6.71
     // (profiles/r05_heavy_rows_ab.txt). RSP_SPMV_VARIANT bit 9 still spreads
-    // every small matrix (A/B), bit 5 keeps every tile on the int32 indices.
-    // A batch re-plans its members itself (rsp_spmv_batch_create). Tiling
-    // never changes the result (canonical summation order).
+    // every small matrix (A/B). A batch re-plans its members itself
+    // (rsp_spmv_batch_create). Tiling never changes the result (canonical
+    // summation order).
     const bool spread = (h->spmv_variant & 512) != 0;
     TilePlan p;
-    make_tile_plan(rp.data(), ci.data(), m, mat->nnz, compute_type,
-                   spread ? spmv_resident_tiles(h, compute_type) : 0,
-                   mat->local_cols, !(h->spmv_variant & 32), p, spmv_row_align(h, compute_type),
-                   !(h->spmv_variant & rsp::kSpmvVariantNoStage));
-    const rsp_an::hvec<SpmvBlock> &blocks = p.blocks;
-    const rsp_an::hvec<SpmvLongRow> &longrows = p.longrows;
-    const int nslots = p.nslots, nint = p.nint;
-    const rsp_an::hvec<int> &cbase = p.cbase;
-    const rsp_an::hvec<uint16_t> &c16 = p.c16;
-    const int64_t nnz_c16 = p.nnz_c16;
+    rsp_plan::make_tile_plan(rp.data(), ci.data(), m, mat->nnz,
+                             handle_plan_options(h, compute_type, mat->local_cols,
+                                                 spread ? spmv_resident_tiles(h, compute_type) : 0),
+                             p);
     // exact layout of this schedule in the matrix's device memory (grown,
     // never shrunk, on a re-plan)
-    SpmvBounds b{blocks.size(), longrows.size(), (size_t)nslots};
-    const SpmvLayout lay = spmv_layout(b, elem_size(compute_type), (int64_t)c16.size(), p.runs.size());
+    const size_t elem = elem_size(compute_type);
+    const rsp_plan::SpmvLayout lay = rsp_plan::spmv_layout({p.blocks.size(), p.longrows.size(), (size_t)p.nslots},
+                                                           elem, (int64_t)p.c16.size(), p.runs.size());
     mat->planned = 0;
     if (lay.bytes > mat->plan_cap || !mat->d_plan) {
         if (mat->d_plan) {
@@ -475,45 +121,29 @@ rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t 
         RSP_CHECK_HIP(hipGetDevice(&mat->plan_device));
     }
     char *buf = (char *)mat->d_plan;
-    if (!blocks.empty()) {
-        RSP_CHECK_HIP(hipMemcpyAsync(buf, blocks.data(), blocks.size() * sizeof(SpmvBlock),
-                                     hipMemcpyHostToDevice, h->stream));
-        RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_cbase, cbase.data(), cbase.size() * sizeof(int),
-                                     hipMemcpyHostToDevice, h->stream));
-        RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_poff, p.poff.data(), p.poff.size() * sizeof(int),
-                                     hipMemcpyHostToDevice, h->stream));
-    }
-    if (!c16.empty())
-        RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_cidx, c16.data(), c16.size() * sizeof(uint16_t),
-                                     hipMemcpyHostToDevice, h->stream));
-    if (!p.runs.empty())
-        RSP_CHECK_HIP(hipMemcpyAsync(buf + lay.off_runs, p.runs.data(), p.runs.size() * sizeof(int),
-                                     hipMemcpyHostToDevice, h->stream));
-    const size_t off_long = lay.off_long, off_part = lay.off_part;
-    if (!longrows.empty())
-        RSP_CHECK_HIP(hipMemcpyAsync(buf + off_long, longrows.data(),
-                                     longrows.size() * sizeof(SpmvLongRow), hipMemcpyHostToDevice,
-                                     h->stream));
+    auto upload = [&](size_t off, const void *src, size_t bytes) {
+        return bytes == 0 ? hipSuccess : hipMemcpyAsync(buf + off, src, bytes, hipMemcpyHostToDevice, h->stream);
+    };
+    RSP_CHECK_HIP(upload(0, p.blocks.data(), p.blocks.size() * sizeof(SpmvBlock)));
+    RSP_CHECK_HIP(upload(lay.off_cbase, p.cbase.data(), p.cbase.size() * sizeof(int)));
+    RSP_CHECK_HIP(upload(lay.off_poff, p.poff.data(), p.poff.size() * sizeof(int)));
+    RSP_CHECK_HIP(upload(lay.off_cidx, p.c16.data(), p.c16.size() * sizeof(uint16_t)));
+    RSP_CHECK_HIP(upload(lay.off_runs, p.runs.data(), p.runs.size() * sizeof(int)));
+    RSP_CHECK_HIP(upload(lay.off_long, p.longrows.data(), p.longrows.size() * sizeof(SpmvLongRow)));
     // partial slots: the long rows' arrival tickets start (and stay) at 0
-    if (nslots > 0)
-        RSP_CHECK_HIP(hipMemsetAsync(buf + off_part, 0, (size_t)nslots * 2 * elem_size(compute_type),
-                                     h->stream));
+    if (p.nslots > 0)
+        RSP_CHECK_HIP(hipMemsetAsync(buf + lay.off_part, 0, (size_t)p.nslots * 2 * elem, h->stream));
     RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
     mat->planned = 1;
     mat->plan_type = compute_type;
-    mat->nblocks = (int)blocks.size();
-    mat->nint = nint;
+    mat->nblocks = (int)p.blocks.size();
+    mat->nint = p.nint;
     mat->plan_gen = plan_new_gen();
-    mat->nlong = (int)longrows.size();
-    mat->nslots = nslots;
+    mat->nlong = (int)p.longrows.size();
+    mat->nslots = p.nslots;
     mat->nnz_s = m > 0 ? rp[(size_t)m] : 0;
-    mat->off_long = off_long;
-    mat->off_part = off_part;
-    mat->off_cbase = lay.off_cbase;
-    mat->off_poff = lay.off_poff;
-    mat->off_cidx = lay.off_cidx;
-    mat->off_runs = lay.off_runs;
-    mat->nnz_c16 = nnz_c16;
+    mat->lay = lay;
+    mat->nnz_c16 = p.nnz_c16;
     mat->nnz_staged = p.nnz_staged;
     return RSP_STATUS_SUCCESS;
 }
@@ -541,14 +171,14 @@ rsp_status_t rsp_api::spmv_run(rsp_handle_t h, rsp_operation_t op, const void *a
     a.y = d_y;
     a.blocks = (const SpmvBlock *)plan;
     a.nblocks = mat->nblocks;
-    a.cbases = (const int *)(plan + mat->off_cbase);
-    a.poffs = (const int *)(plan + mat->off_poff);
-    a.cidx = (const unsigned short *)(plan + mat->off_cidx);
-    a.runs = (const int *)(plan + mat->off_runs);
+    a.cbases = (const int *)(plan + mat->lay.off_cbase);
+    a.poffs = (const int *)(plan + mat->lay.off_poff);
+    a.cidx = (const unsigned short *)(plan + mat->lay.off_cidx);
+    a.runs = (const int *)(plan + mat->lay.off_runs);
     a.cmax = mat->cols > 0 ? (int)(mat->cols - 1) : 0;
-    a.longrows = (const SpmvLongRow *)(plan + mat->off_long);
+    a.longrows = (const SpmvLongRow *)(plan + mat->lay.off_long);
     a.nlong = mat->nlong;
-    a.partials = plan + mat->off_part;
+    a.partials = plan + mat->lay.off_part;
     if (compute_type == RSP_R_64F) {
         a.alpha = *(const double *)alpha;
         a.beta = *(const double *)beta;
@@ -630,13 +260,19 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     // same A with several right-hand sides), and a batch never shares
     // tickets with single calls of its matrices.
     const int64_t R = spmv_resident_tiles(h, compute_type);
-    const bool spread_ok = !(h->spmv_variant & 16), c16_ok = !(h->spmv_variant & 32);
-    const bool stage_ok = !(h->spmv_variant & rsp::kSpmvVariantNoStage);
+    const bool spread_ok = !(h->spmv_variant & 16);
     rsp_an::hvec<TilePlan> plans((size_t)count);
-    // layout: per launch [entries | tiles | tile column bases | long rows |
-    // 16-bit column offsets of each matrix | long-row partials and tickets of
-    // each matrix (zero)], each 16-B aligned
-    struct Span { int first, count; size_t off_e, off_t, off_c, off_k, off_l; rsp_an::hvec<size_t> off_16, off_p, off_r; };
+    // layout: per launch [entries | tiles | tile column bases | tile record
+    // offsets | long rows | 16-bit column offsets of each matrix | runs and
+    // records of each matrix | long-row partials and tickets of each matrix
+    // (zero)], each 16-B aligned
+    struct Region { size_t off, len; };
+    struct Span {
+        int first, count, nt, nl;  // members [first, first + count); their tiles and long rows in this launch
+        rsp_an::hvec<Region> reg;  // in layout order: the five shared regions, then three per member
+        enum { kEntries, kTiles, kCbases, kPoffs, kLongRows, kC16, kRuns, kPartials };
+        const Region &at(int kind, int q) const { return reg[kind < kC16 ? kind : kC16 + (kind - kC16) * count + q]; }
+    };
     rsp_an::hvec<Span> spans;
     size_t bytes = 0;
     auto tile_range = [part](const TilePlan &p, int *t0, int *t1) {
@@ -644,63 +280,52 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
         *t1 = part == 1 ? p.nint : (int)p.blocks.size();
     };
     for (int first = 0; first < count; first += rsp::kSpmvBatchMax) {
-        Span sp{first, std::min(rsp::kSpmvBatchMax, count - first), 0, 0, 0, 0, 0, {}, {}, {}};
+        Span sp{first, std::min(rsp::kSpmvBatchMax, count - first), 0, 0, {}};
         rsp_an::hvec<rsp_an::hvec<int>> rps((size_t)sp.count), cis((size_t)sp.count);
-        int64_t nt_full = 0, nnz_all = 0;
+        auto plan_members = [&](int64_t spread_all, int64_t nnz_all) {  // spread_all: of the launch, 0 = full tiles
+            sp.nt = 0;
+            for (int q = 0; q < sp.count; q++) {
+                rsp_spmat_t A = mats[first + q];
+                const int64_t nnz_q = A->rows > 0 ? rps[q][(size_t)A->rows] : 0;
+                const int64_t share =
+                    spread_all > 0 ? std::max<int64_t>(1, spread_all * nnz_q / std::max<int64_t>(1, nnz_all)) : 0;
+                TilePlan &p = plans[first + q];
+                rsp_plan::make_tile_plan(rps[q].data(), cis[q].data(), (int)A->rows, A->nnz,
+                                         handle_plan_options(h, compute_type, A->local_cols, share), p);
+                int t0, t1;
+                tile_range(p, &t0, &t1);
+                sp.nt += t1 - t0;
+            }
+        };
+        int64_t nnz_all = 0;
         for (int q = 0; q < sp.count; q++) {
             rsp_spmat_t A = mats[first + q];
             rsp_status_t st = download_pattern(h, A, rps[q], cis[q]);
             if (st != RSP_STATUS_SUCCESS) return st;
-            make_tile_plan(rps[q].data(), cis[q].data(), (int)A->rows, A->nnz, compute_type, 0,
-                           A->local_cols, c16_ok, plans[first + q], spmv_row_align(h, compute_type), stage_ok);
-            int t0, t1;
-            tile_range(plans[first + q], &t0, &t1);
-            nt_full += t1 - t0;
             nnz_all += A->rows > 0 ? rps[q][(size_t)A->rows] : 0;
         }
-        if (spread_ok && nt_full < R)
-            for (int q = 0; q < sp.count; q++) {
-                rsp_spmat_t A = mats[first + q];
-                const int64_t nnz_q = A->rows > 0 ? rps[q][(size_t)A->rows] : 0;
-                const int64_t share = std::max<int64_t>(1, R * nnz_q / std::max<int64_t>(1, nnz_all));
-                make_tile_plan(rps[q].data(), cis[q].data(), (int)A->rows, A->nnz, compute_type,
-                               share, A->local_cols, c16_ok, plans[first + q],
-                               spmv_row_align(h, compute_type), stage_ok);
-            }
-        int nt = 0, nl = 0;
+        plan_members(0, nnz_all);
+        if (spread_ok && sp.nt < R) plan_members(R, nnz_all);
         for (int q = 0; q < sp.count; q++) {
             const TilePlan &p = plans[first + q];
             rsp_spmat_t A = mats[first + q];
             // the long rows index partial slots of the matrix's own workspace
             if ((int)p.longrows.size() != A->nlong || p.nslots != A->nslots)
                 return RSP_STATUS_INTERNAL_ERROR;
-            int t0, t1;
-            tile_range(p, &t0, &t1);
-            nt += t1 - t0;
-            nl += part == 1 ? 0 : (int)p.longrows.size();
+            sp.nl += part == 1 ? 0 : (int)p.longrows.size();
         }
-        sp.off_e = bytes;
-        bytes += (size_t)sp.count * sizeof(rsp::SpmvBatchEntry);
-        sp.off_t = bytes;
-        bytes += (size_t)nt * sizeof(SpmvBlock);
-        sp.off_c = bytes;
-        bytes += ((size_t)nt * sizeof(int) + 15) & ~(size_t)15;
-        sp.off_k = bytes;
-        bytes += ((size_t)nt * sizeof(int) + 15) & ~(size_t)15;
-        sp.off_l = bytes;
-        bytes += ((size_t)nl * sizeof(SpmvLongRow) + 15) & ~(size_t)15;
-        for (int q = 0; q < sp.count; q++) {
-            sp.off_16.push_back(bytes);
-            bytes += (plans[first + q].c16.size() * sizeof(uint16_t) + 15) & ~(size_t)15;
-        }
-        for (int q = 0; q < sp.count; q++) {
-            sp.off_r.push_back(bytes);
-            bytes += (plans[first + q].runs.size() * sizeof(int) + 15) & ~(size_t)15;
-        }
-        for (int q = 0; q < sp.count; q++) {
-            sp.off_p.push_back(bytes);
-            const size_t pb = (size_t)plans[first + q].nslots * 2 * elem_size(compute_type);
-            bytes += (pb + 15) & ~(size_t)15;
+        sp.reg = {{0, (size_t)sp.count * sizeof(rsp::SpmvBatchEntry)},
+                  {0, (size_t)sp.nt * sizeof(SpmvBlock)},
+                  {0, (size_t)sp.nt * sizeof(int)},
+                  {0, (size_t)sp.nt * sizeof(int)},
+                  {0, (size_t)sp.nl * sizeof(SpmvLongRow)}};
+        for (int q = 0; q < sp.count; q++) sp.reg.push_back({0, plans[first + q].c16.size() * sizeof(uint16_t)});
+        for (int q = 0; q < sp.count; q++) sp.reg.push_back({0, plans[first + q].runs.size() * sizeof(int)});
+        for (int q = 0; q < sp.count; q++)
+            sp.reg.push_back({0, (size_t)plans[first + q].nslots * 2 * elem_size(compute_type)});
+        for (Region &r : sp.reg) {
+            r.off = bytes;
+            bytes += (r.len + 15) & ~(size_t)15;
         }
         spans.push_back(sp);
     }
@@ -711,88 +336,73 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
     // written by nothing else here) are its own.
     {
         size_t end = 0;
-        auto region = [&](size_t off, size_t len) {
-            const bool ok = off >= end && off + len <= bytes;
-            end = off + len;
-            return ok;
-        };
-        for (const Span &sp : spans) {
-            int nt = 0, nl = 0;
-            for (int q = 0; q < sp.count; q++) {
-                int t0, t1;
-                tile_range(plans[sp.first + q], &t0, &t1);
-                nt += t1 - t0;
-                nl += part == 1 ? 0 : (int)plans[sp.first + q].longrows.size();
+        for (const Span &sp : spans)
+            for (const Region &r : sp.reg) {
+                if (r.off < end || r.off + r.len > bytes) return RSP_STATUS_INTERNAL_ERROR;
+                end = r.off + r.len;
             }
-            bool ok = region(sp.off_e, (size_t)sp.count * sizeof(rsp::SpmvBatchEntry)) &&
-                      region(sp.off_t, (size_t)nt * sizeof(SpmvBlock)) && region(sp.off_c, (size_t)nt * sizeof(int)) &&
-                      region(sp.off_k, (size_t)nt * sizeof(int)) && region(sp.off_l, (size_t)nl * sizeof(SpmvLongRow));
-            for (int q = 0; ok && q < sp.count; q++) ok = region(sp.off_16[q], plans[sp.first + q].c16.size() * 2);
-            for (int q = 0; ok && q < sp.count; q++) ok = region(sp.off_r[q], plans[sp.first + q].runs.size() * 4);
-            for (int q = 0; ok && q < sp.count; q++)
-                ok = region(sp.off_p[q], (size_t)plans[sp.first + q].nslots * 2 * elem_size(compute_type));
-            if (!ok) return RSP_STATUS_INTERNAL_ERROR;
-        }
     }
     if (bytes > 0) RSP_CHECK_HIP(hipMalloc(&b->d_mem, bytes));
     rsp_an::hvec<unsigned char> host(bytes);
+    bool fits = true;  // every copy of the fill lies inside the region the layout gave it
     for (const Span &sp : spans) {
+        auto dev = [&](int kind, int q = 0) { return (char *)b->d_mem + sp.at(kind, q).off; };
+        auto put = [&](int kind, int q, size_t at, const void *src, size_t n) {
+            const Region &r = sp.at(kind, q);
+            if (at + n > r.len)
+                fits = false;
+            else if (n > 0)
+                memcpy(host.data() + r.off + at, src, n);
+        };
         rsp::SpmvBatchArgs a{};
-        a.entries = (const rsp::SpmvBatchEntry *)((char *)b->d_mem + sp.off_e);
-        a.tiles = (const SpmvBlock *)((char *)b->d_mem + sp.off_t);
-        a.cbases = (const int *)((char *)b->d_mem + sp.off_c);
-        a.poffs = (const int *)((char *)b->d_mem + sp.off_k);
-        a.longrows = (const SpmvLongRow *)((char *)b->d_mem + sp.off_l);
+        a.entries = (const rsp::SpmvBatchEntry *)dev(Span::kEntries);
+        a.tiles = (const SpmvBlock *)dev(Span::kTiles);
+        a.cbases = (const int *)dev(Span::kCbases);
+        a.poffs = (const int *)dev(Span::kPoffs);
+        a.longrows = (const SpmvLongRow *)dev(Span::kLongRows);
         a.count = sp.count;
         for (int q = 0; q <= rsp::kSpmvBatchMax; q++)
             a.tiles_at.begin[q] = a.longs_at.begin[q] = INT_MAX;
-        int nt = 0, nl = 0;
+        size_t nt = 0, nl = 0;
         for (int q = 0; q < sp.count; q++) {
             rsp_spmat_t A = mats[sp.first + q];
             const TilePlan &p = plans[sp.first + q];
             int t0, t1;
             tile_range(p, &t0, &t1);
-            const int nlq = part == 1 ? 0 : (int)p.longrows.size();
+            const size_t ntq = (size_t)(t1 - t0), nlq = part == 1 ? 0 : p.longrows.size();
             rsp::SpmvBatchEntry e{};
             e.rowptr = A->rowptr;
             e.colidx = A->colidx;
             e.vals = A->vals;
             e.x = d_x[sp.first + q];
             e.y = d_y[sp.first + q];
-            e.partials = (void *)((char *)b->d_mem + sp.off_p[q]);  // this member's own
-            e.cidx = (const unsigned short *)((char *)b->d_mem + sp.off_16[q]);
-            e.runs = (const int *)((char *)b->d_mem + sp.off_r[q]);
+            e.partials = (void *)dev(Span::kPartials, q);  // this member's own
+            e.cidx = (const unsigned short *)dev(Span::kC16, q);
+            e.runs = (const int *)dev(Span::kRuns, q);
             e.cmax = A->cols > 0 ? (int)(A->cols - 1) : 0;
             e.nnz = A->nnz_s;
             e.vector_ok = ((((uintptr_t)A->colidx) | ((uintptr_t)A->vals)) & 15) == 0;
-            memcpy(host.data() + sp.off_e + (size_t)q * sizeof(e), &e, sizeof(e));
-            a.tiles_at.begin[q] = nt;
-            a.longs_at.begin[q] = nl;
+            put(Span::kEntries, 0, (size_t)q * sizeof(e), &e, sizeof(e));
+            a.tiles_at.begin[q] = (int)nt;
+            a.longs_at.begin[q] = (int)nl;
             for (int t = t0; t < t1; t++)
-                if (p.cbase[(size_t)t] != -1) b->entries_16bit += p.blocks[(size_t)t].k1 - p.blocks[(size_t)t].k0;
-            b->tiles += t1 - t0;
-            if (t1 > t0) {
-                memcpy(host.data() + sp.off_t + (size_t)nt * sizeof(SpmvBlock), p.blocks.data() + t0,
-                       (size_t)(t1 - t0) * sizeof(SpmvBlock));
-                memcpy(host.data() + sp.off_c + (size_t)nt * sizeof(int), p.cbase.data() + t0,
-                       (size_t)(t1 - t0) * sizeof(int));
-                memcpy(host.data() + sp.off_k + (size_t)nt * sizeof(int), p.poff.data() + t0,
-                       (size_t)(t1 - t0) * sizeof(int));
-            }
-            if (nlq > 0)
-                memcpy(host.data() + sp.off_l + (size_t)nl * sizeof(SpmvLongRow), p.longrows.data(),
-                       (size_t)nlq * sizeof(SpmvLongRow));
-            if (!p.c16.empty())
-                memcpy(host.data() + sp.off_16[q], p.c16.data(), p.c16.size() * sizeof(uint16_t));
-            if (!p.runs.empty())
-                memcpy(host.data() + sp.off_r[q], p.runs.data(), p.runs.size() * sizeof(int));
-            nt += t1 - t0;
+                if (p.cbase[(size_t)t] != rsp_plan::kCbaseInt32)
+                    b->entries_16bit += p.blocks[(size_t)t].k1 - p.blocks[(size_t)t].k0;
+            b->tiles += (int64_t)ntq;
+            put(Span::kTiles, 0, nt * sizeof(SpmvBlock), p.blocks.data() + t0, ntq * sizeof(SpmvBlock));
+            put(Span::kCbases, 0, nt * sizeof(int), p.cbase.data() + t0, ntq * sizeof(int));
+            put(Span::kPoffs, 0, nt * sizeof(int), p.poff.data() + t0, ntq * sizeof(int));
+            put(Span::kLongRows, 0, nl * sizeof(SpmvLongRow), p.longrows.data(), nlq * sizeof(SpmvLongRow));
+            put(Span::kC16, q, 0, p.c16.data(), p.c16.size() * sizeof(uint16_t));
+            put(Span::kRuns, q, 0, p.runs.data(), p.runs.size() * sizeof(int));
+            nt += ntq;
             nl += nlq;
         }
-        a.tiles_at.begin[sp.count] = nt;
-        a.longs_at.begin[sp.count] = nl;
+        a.tiles_at.begin[sp.count] = (int)nt;
+        a.longs_at.begin[sp.count] = (int)nl;
         b->launches.push_back(a);
     }
+    if (!fits) return RSP_STATUS_INTERNAL_ERROR;
     // the image is value-initialised, so every member's long-row partials and
     // tickets go up as 0 (tickets start, and stay, at 0 between launches)
     // (on the handle's stream; create is host-blocking and `host` is freed on return)
@@ -805,140 +415,6 @@ static rsp_status_t spmv_batch_create(rsp_handle_t h, int count, const rsp_spmat
         b->plan_gen.push_back(mats[j]->plan_gen);
     }
     *batch = b.release();
-    return RSP_STATUS_SUCCESS;
-}
-
-// A packed record's geometry for `type`: vector width, slot-field words.
-static void pack_geometry(rsp_datatype_t type, int *vw, int *iw) {
-    *vw = type == RSP_R_64F ? SpmvTile<double>::kVec : SpmvTile<float>::kVec;
-    *iw = rsp_pack::index_words(rsp::kSpmvThreads, rsp::kSpmvIter * *vw);
-}
-
-// rsp_spmv_plan_stats: what one call over the schedule of a host pattern
-// reads besides the values, x and y (see include/rsp.h for the rule).
-static rsp_status_t spmv_plan_stats(int m, const int *rp, const int *ci, int64_t nnz, rsp_datatype_t type,
-                                    int64_t *out) {
-    if (m < 0 || (m > 0 && (!rp || !ci)) || !out) return RSP_STATUS_INVALID_VALUE;
-    if (type != RSP_R_64F && type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
-    TilePlan p;
-    make_tile_plan(rp, ci, m, nnz, type, 0, -1, true, p);
-    int vw, iw;
-    pack_geometry(type, &vw, &iw);
-    int64_t staged = 0, idx = 0, desc = 0, rows16 = 0, rowptr = 0;
-    for (size_t t = 0; t < p.blocks.size(); t++) {
-        const SpmvBlock &b = p.blocks[t];
-        const int cb = p.cbase[t], po = p.poff[t];
-        const int64_t len = b.k1 - b.k0, nrows = b.r1 > b.r0 ? b.r1 - b.r0 : 0;
-        idx += po >= 0 ? 4LL * iw : cb == -1 ? 4 * len : 2 * len;
-        if (cb <= -2) {
-            const int code = -2 - cb, nr = code & 255;
-            staged++;
-            desc += nr == 255 ? 8 + 2LL * p.runs[2 * (size_t)(code >> 8) + 1] : 8LL * (nr + 1);
-        }
-        if (po >= 0 && (po & 1))
-            rows16 += 4LL * rsp_pack::row_words((int)nrows);
-        else
-            rowptr += 4 * (nrows + 1);
-    }
-    out[0] = (int64_t)p.blocks.size();
-    out[1] = p.tiles_packed;
-    out[2] = p.nnz_packed;
-    out[3] = 24 * (int64_t)p.blocks.size() + idx + desc + rows16;
-    out[4] = rowptr;
-    out[5] = staged;
-    out[6] = idx;
-    out[7] = rows16;
-    return RSP_STATUS_SUCCESS;
-}
-
-// rsp_spmv_plan_host: the schedule of a host pattern, every 16-bit / staged
-// column decoded back and compared with the pattern; a packed tile's slots
-// are read from its record's fields, whose padding must be 0, and its packed
-// row offsets are compared with the row offsets.
-static rsp_status_t spmv_plan_host(int m, const int *rp, const int *ci, int64_t nnz, rsp_datatype_t type,
-                                   int64_t *tiles, int64_t *e16, int64_t *est) {
-    if (m < 0 || (m > 0 && (!rp || !ci)) || !tiles || !e16 || !est) return RSP_STATUS_INVALID_VALUE;
-    if (type != RSP_R_64F && type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
-    TilePlan p;
-    make_tile_plan(rp, ci, m, nnz, type, 0, -1, true, p);
-    const int ucap = type == RSP_R_64F ? SpmvTile<double>::kStageSlots : SpmvTile<float>::kStageSlots;
-    int vw, iw;
-    pack_geometry(type, &vw, &iw);
-    const int pack_mode = spmv_pack_mode();
-    if (p.poff.size() != p.blocks.size()) return RSP_STATUS_INTERNAL_ERROR;
-    int64_t npk = 0, epk = 0;
-    for (size_t t = 0; t < p.blocks.size(); t++) {
-        const SpmvBlock &b = p.blocks[t];
-        const int cb = p.cbase[t], po = p.poff[t];
-        const uint32_t *rec = nullptr;
-        if (po >= 0) {  // the record: a staged, eligible tile; inside `runs`, after the descriptors
-            const int nrows = b.r1 - b.r0, kb = b.k0 & ~(vw - 1);
-            const size_t w0 = (size_t)(po >> 1), words = (size_t)iw + ((po & 1) ? rsp_pack::row_words(nrows) : 0);
-            if (cb > -2 || b.r1 < 0 || pack_mode == 0 || (po & 1) != (pack_mode >= 2) ||
-                !rsp_pack::eligible(rsp::kSpmvThreads, rsp::kSpmvIter * vw, b.k1 - b.k0) || (w0 & 3) ||
-                w0 + words > p.runs.size())
-                return RSP_STATUS_INTERNAL_ERROR;
-            rec = reinterpret_cast<const uint32_t *>(p.runs.data()) + w0;
-            const int nwt = iw / rsp::kSpmvThreads;
-            for (int tid = 0; tid < rsp::kSpmvThreads; tid++)  // fields outside [k0, k1) are 0
-                for (int f = 0; f < rsp::kSpmvIter * vw; f++) {
-                    const long long e = (long long)kb + (long long)((f / vw) * rsp::kSpmvThreads + tid) * vw + f % vw;
-                    if ((e < b.k0 || e >= b.k1) && rsp_pack::get_field(rec + (size_t)tid * nwt, f) != 0)
-                        return RSP_STATUS_INTERNAL_ERROR;
-                }
-            if (po & 1)
-                for (int i = 0; i <= nrows; i++)
-                    if (rsp_pack::unpack_row(rec + iw, i) + kb != rp[b.r0 + i]) return RSP_STATUS_INTERNAL_ERROR;
-            npk++;
-            epk += b.k1 - b.k0;
-        }
-        auto slot_of = [&](int k) {
-            return rec ? (int)rsp_pack::unpack_slot(rec, b.k0, k, vw, rsp::kSpmvIter, rsp::kSpmvThreads)
-                       : (int)p.c16[(size_t)k];
-        };
-        if (cb == -1) continue;
-        for (int k = b.k0; k < b.k1; k++) {
-            int col;
-            if (cb >= 0) {
-                col = cb + p.c16[(size_t)k];
-            } else {
-                const int code = -2 - cb, nr = code & 255, off = code >> 8;
-                if (nr == 255) {  // list mode (fp64): {base, U}, then U uint16 offsets
-                    if (type != RSP_R_64F) return RSP_STATUS_INTERNAL_ERROR;
-                    if ((size_t)2 * off + 2 > p.runs.size()) return RSP_STATUS_INTERNAL_ERROR;
-                    const int *r = p.runs.data() + 2 * (size_t)off;
-                    const int U = r[1];
-                    if (U < 1 || U > ucap || (size_t)2 * off + 2 + 2 * (size_t)((U + 3) / 4) > p.runs.size())
-                        return RSP_STATUS_INTERNAL_ERROR;
-                    const uint16_t *o = reinterpret_cast<const uint16_t *>(r + 2);
-                    for (int u = 1; u < U; u++)
-                        if (o[u] <= o[u - 1]) return RSP_STATUS_INTERNAL_ERROR;
-                    const int u = slot_of(k);
-                    if (u >= U) return RSP_STATUS_INTERNAL_ERROR;
-                    if (r[0] + o[u] != ci[k]) return RSP_STATUS_INTERNAL_ERROR;
-                    continue;
-                }
-                if (nr < 1 || nr > rsp::kStageRuns || (size_t)2 * (off + nr + 1) > p.runs.size())
-                    return RSP_STATUS_INTERNAL_ERROR;
-                const int *r = p.runs.data() + 2 * (size_t)off;
-                const int U = r[2 * nr + 1];
-                if (r[1] != 0 || U > ucap) return RSP_STATUS_INTERNAL_ERROR;
-                for (int j = 1; j <= nr; j++)
-                    if (r[2 * j + 1] <= r[2 * j - 1] || (j < nr && r[2 * j] <= r[2 * j - 2] + (r[2 * j + 1] - r[2 * j - 1]) - 1))
-                        return RSP_STATUS_INTERNAL_ERROR;
-                const int u = slot_of(k);
-                if (u >= U) return RSP_STATUS_INTERNAL_ERROR;
-                int j = 0;
-                while (j + 1 < nr && r[2 * (j + 1) + 1] <= u) j++;
-                col = r[2 * j] + (u - r[2 * j + 1]);
-            }
-            if (col != ci[k]) return RSP_STATUS_INTERNAL_ERROR;
-        }
-    }
-    if (npk != p.tiles_packed || epk != p.nnz_packed) return RSP_STATUS_INTERNAL_ERROR;
-    *tiles = (int64_t)p.blocks.size();
-    *e16 = p.nnz_c16;
-    *est = p.nnz_staged;
     return RSP_STATUS_SUCCESS;
 }
 
@@ -1232,13 +708,30 @@ rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_in
                                 rsp_datatype_t compute_type, int64_t *tiles, int64_t *entries_16bit,
                                 int64_t *entries_staged) {
     return guarded([&] {
-        return spmv_plan_host(m, row_offsets, col_ind, nnz, compute_type, tiles, entries_16bit, entries_staged);
+        if (m < 0 || (m > 0 && (!row_offsets || !col_ind)) || !tiles || !entries_16bit || !entries_staged)
+            return RSP_STATUS_INVALID_VALUE;
+        if (compute_type != RSP_R_64F && compute_type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
+        const PlanOptions o = rsp_plan::plan_options(compute_type);
+        TilePlan p;
+        rsp_plan::make_tile_plan(row_offsets, col_ind, m, nnz, o, p);
+        if (!rsp_plan::plan_verify(row_offsets, col_ind, m, o, p)) return RSP_STATUS_INTERNAL_ERROR;
+        *tiles = (int64_t)p.blocks.size();
+        *entries_16bit = p.nnz_c16;
+        *entries_staged = p.nnz_staged;
+        return RSP_STATUS_SUCCESS;
     });
 }
 
 rsp_status_t rsp_spmv_plan_stats(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
                                  rsp_datatype_t compute_type, int64_t stats[8]) {
-    return guarded([&] { return spmv_plan_stats(m, row_offsets, col_ind, nnz, compute_type, stats); });
+    return guarded([&] {
+        if (m < 0 || (m > 0 && (!row_offsets || !col_ind)) || !stats) return RSP_STATUS_INVALID_VALUE;
+        if (compute_type != RSP_R_64F && compute_type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
+        TilePlan p;
+        rsp_plan::make_tile_plan(row_offsets, col_ind, m, nnz, rsp_plan::plan_options(compute_type), p);
+        rsp_plan::plan_stats(p, compute_type, stats);
+        return RSP_STATUS_SUCCESS;
+    });
 }
 
 }  // the C ABI

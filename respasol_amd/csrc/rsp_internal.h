@@ -1,7 +1,8 @@
 // rsp_internal.h — what the host units of librsp.so share: the three structs
 // behind the opaque handles of include/rsp.h, the status macros, guarded()
 // and the few functions one unit calls in another (namespace rsp_api).
-//   rsp_api.cpp           handle, matrix descriptor, SpMV (plan, run, batch)
+//   rsp_api.cpp           handle, matrix descriptor, SpMV (plan upload, run, batch)
+//   spmv_plan.cpp         the SpMV planner (spmv_plan.h; no HIP calls)
 //   api_ilu_analysis.cpp  ILU(0) analysis, the solve plans, the plan queries
 //   api_ilu_solve.cpp     factor and triangular solves, flow give-up recovery
 //   api_krylov.cpp        BiCGStab, GMRES, rsp_dot, rsp_orthogonalize
@@ -24,6 +25,7 @@
 
 #include "rsp_kernels.h"
 #include "ilu_analysis.h"
+#include "spmv_plan.h"
 
 struct rsp_context {
     int device;
@@ -61,13 +63,12 @@ struct rsp_spmat {
     // schedule state
     int planned;                // d_plan holds a schedule for plan_type / local_cols
     int plan_device;            // device d_plan was allocated on
-    void *d_plan;               // [tiles | long rows | partials | col bases | 16-bit offsets]
+    void *d_plan;               // [tiles | long rows | partials | col bases | record offsets | 16-bit offsets | runs, records]
     size_t plan_cap;            // bytes allocated at d_plan
     rsp_datatype_t plan_type;
     int nblocks, nlong, nslots;
     int nnz_s;                  // rowptr[rows] seen by the planner
-    size_t off_long, off_part;  // byte offsets inside d_plan
-    size_t off_cbase, off_poff, off_cidx, off_runs;
+    rsp_plan::SpmvLayout lay;   // byte offsets inside d_plan
     int64_t nnz_c16;            // entries read through 16-bit column offsets or slot indices
     int64_t nnz_staged;         // ... of which in staged tiles (x staged in LDS)
     int64_t local_cols;         // rsp_spmat_set_local_cols (-1: not split)

@@ -86,6 +86,8 @@ struct SpmvArgs {
     // <= -2 a staged tile: code = -2 - cbase, its run descriptors at
     // runs[2 (code >> 8) ..], (code & 255) of them + a sentinel, and its
     // 16-bit values are LDS slot indices of the tile's distinct columns
+    // (the host's encoder / decoder of this and of poffs: spmv_plan.h
+    // stage_encode / stage_decode, pack_encode / pack_decode)
     const int *cbases;
     const unsigned short *cidx;   // 16-bit column offsets / slot indices (tiles with cbases != -1)
     const int *runs;              // staged tiles: {first column, first slot} per run, {0, slots} last

@@ -169,7 +169,7 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// A STAGED tile (round 4; plan: rsp_api.cpp make_tile_plan). Gathering x
+// A STAGED tile (round 4; plan: spmv_plan.cpp encode_columns). Gathering x
 // lane by lane costs the vector-memory path about one TA cycle per lane —
 // the bound of the plain tile (counters) — while a mesh tile's
 // 2-4 k entries read only ~900-1600 distinct columns, in a few contiguous

@@ -1,6 +1,6 @@
-// spmv_pack.h — the packed record of a staged SpMV tile (rsp_api.cpp
-// make_tile_plan writes it, spmv.hip stream_products_staged / spmv_tile read
-// it, rsp_spmv_plan_host decodes it). Plain C++: no HIP dependency, so the
+// spmv_pack.h — the packed record of a staged SpMV tile (spmv_plan.cpp
+// pack_staged_tiles writes it, spmv.hip stream_products_staged / spmv_tile
+// read it, rsp_plan::plan_verify decodes it). Plain C++: no HIP dependency, so the
 // arithmetic also builds into the stand-alone sanitizer check
 // (drivers/spmv_pack_check.cpp, make asan-pack).
 //

@@ -271,7 +271,7 @@ def stencil_case(dtype, spec):
 
 def heavy_pass_rows(lens, cap, maxrows):
     """The rows that reduce_heavy_rows sums under the full-tile schedule
-    (rsp_api.cpp build_spmv_plan, spmv.hip reduce_tile_rows): consecutive rows
+    (spmv_plan.cpp build_spmv_plan, spmv.hip reduce_tile_rows): consecutive rows
     of <= 256 entries packed greedily into tiles of <= cap entries / maxrows
     rows; a tile takes L = 1, 2, 4 or 8 lanes per row, and with L < 8 its rows
     of more than 32 L entries go to the second pass."""

@@ -96,3 +96,48 @@ def test_analysis_host_clean_under_tsan_and_asan(an_exes, name, scale):
         assert p.returncode == 0, err
         digests.add(p.stdout.split()[-1])
     assert len(digests) == 1  # the same plan from both builds
+
+
+PLAN_TSAN = os.path.join(ROOT, "respasol_amd", "build", "asan", "spmv_plan_check_tsan")
+PLAN_ASAN = os.path.join(ROOT, "respasol_amd", "build", "asan", "spmv_plan_check_asan")
+
+
+@pytest.fixture(scope="module")
+def plan_exes():
+    """The SpMV planner (csrc/spmv_plan.cpp: parallel column encoding and
+    record packing) under ThreadSanitizer and under ASan + UBSan
+    (respasol_amd/drivers/spmv_plan_check.cpp)."""
+    if shutil.which("g++") is None or shutil.which("make") is None:
+        pytest.skip("g++/make not available")
+    r = subprocess.run(["make", "-s", "-C", CSRC, "tsan-plan", "asan-plan"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return PLAN_TSAN, PLAN_ASAN
+
+
+@pytest.mark.parametrize("name,scale", [("atmosmodd", 0.05), ("cage13", 0.3), ("dc1", 0.3), ("ASIC_320ks", 0.1)])
+def test_spmv_planner_clean_under_tsan_and_asan(plan_exes, name, scale):
+    """Every option set's plan (default, spread, split, row-aligned, no 16-bit
+    offsets, no staged tiles; fp64 and fp32) verifies, is the same when built
+    twice and the same from both builds, and no sanitizer reports; 4 worker
+    threads. atmosmodd: runs tiles and packed records; cage13: list tiles (at
+    0.3 the fp64 default plan stages 2243721 of 2243827 entries in them); dc1:
+    hub rows (long-row chunks, int32 tiles)."""
+    env = dict(os.environ, OMP_NUM_THREADS="4", TSAN_OPTIONS="halt_on_error=1",
+               ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    outs = []
+    for exe in plan_exes:
+        p = subprocess.run([exe, name, str(scale)], env=env, capture_output=True, text=True, timeout=300)
+        ok, err = _clean(p)
+        assert ok and "ThreadSanitizer" not in err, err
+        assert p.returncode == 0, err
+        outs.append(p.stdout)
+    assert len(outs[0].splitlines()) == 14 and outs[0] == outs[1]
+    if name == "cage13":  # list tiles are there: fp64 only, and gone with RSP_SPMV_STAGE_LIST=0 (a further run)
+        f64, f32 = (outs[0].splitlines()[i].split() for i in (0, 7))
+        assert f64[1:3] == ["f64", "default"] and int(f64[8]) > 0 and f32[1:3] == ["f32", "default"] and int(f32[8]) == 0
+        p = subprocess.run([plan_exes[1], name, str(scale)], env=dict(env, RSP_SPMV_STAGE_LIST="0"),
+                           capture_output=True, text=True, timeout=300)
+        assert _clean(p)[0] and p.returncode == 0, p.stdout + p.stderr
+        nolist = p.stdout.splitlines()[0].split()
+        assert nolist[1:3] == ["f64", "default"] and int(nolist[8]) == 0
