@@ -1,6 +1,6 @@
 // api_ilu_analysis.cpp — the ILU(0) analysis of include/rsp.h: the info
 // object's lifecycle, the device half of the symbolic factor
-// (ilu_analysis.hip) overlapped with the host plans (ilu_analysis.cpp), their
+// (ilu_analysis.hip) overlapped with the host plans (ilu_analysis.cpp, ilu_plan_*.cpp), their
 // upload, the L / L^T solve plans built on a worker thread and the U plan,
 // and the plan queries. Mirrors the analysis calls of the reference driver
 // (GPU/ilu0.cu:82-252); the factor and the solves: api_ilu_solve.cpp.

@@ -10,53 +10,12 @@
 #define RSP_ILU_ANALYSIS_H
 
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <exception>
-#include <functional>
-#include <thread>
-#include <utility>
-#include <vector>
 
 #include "rsp.h"
 #include "host_pool.h"
 #include "rsp_kernels.h"
 
 namespace rsp_an {
-
-// A helper thread of the analysis whose exception (std::bad_alloc from the
-// pool, say) is carried to join(), which rethrows it in the caller; the
-// destructor joins too, so a caller that unwinds first never leaves it
-// running over the caller's locals (nor calls std::terminate).
-class Task {
-    std::exception_ptr err_;
-    std::thread t_;
-
-  public:
-    template <typename F>
-    explicit Task(F f) : t_([this, f] {
-          try {
-              f();
-          } catch (...) {
-              err_ = std::current_exception();
-          }
-      }) {}
-    Task(const Task &) = delete;
-    Task &operator=(const Task &) = delete;
-    void join() {
-        if (t_.joinable()) t_.join();
-        if (err_) std::rethrow_exception(std::exchange(err_, nullptr));
-    }
-    ~Task() {
-        if (t_.joinable()) t_.join();
-    }
-};
-
-inline int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
 
 struct SolvePlan {
     hvec<int> sbase;   // per level: first flat term of its padded short rows, -1 = none
@@ -74,7 +33,7 @@ struct SolvePlan {
     int nterm = 0;           // flat terms (tpos.size() once the terms are built; >= 1 then)
 };
 
-// Symbolic ILU(0) data (built by ilu_symbolic below).
+// Symbolic ILU(0) data (built by plan_symbolic below, or on the device).
 struct IluSymbolic {
     hvec<int> upd_ptr, upd_l, upd_u, lord, lend;
     hvec<int> stage;  // per lower position: its intra-row stage
@@ -181,6 +140,8 @@ constexpr int kPhases = 6;  // phase slots of Phases::ms (marks in call order)
 //   plan_factor:   the factor plan, FacRow records, slot layout, flow runs
 //                  (needs sym.upd_ptr / upd_l / upd_u / stage);
 //   plan_rest:     both (the solves on a second thread).
+// Defined in ilu_plan_solve.cpp (plan_solves*, plan_u), ilu_plan_factor.cpp
+// (plan_factor, factor_thin_rows), ilu_blocks.cpp (blocks), else ilu_analysis.cpp.
 rsp_status_t plan_validate(int n, const int *rp, const int *ci, IluHostPlan &hp);
 // The rows of the L DAG's levels the factor runs thin (needs the levels and
 // sym.upd_ptr): the only rows whose update pairs the factor plan reads.
@@ -217,33 +178,21 @@ bool blocks_wanted(int n, int nlev);
 bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, BlkPlanHost &bp);
 // Build the U DAG's levels and solve plan (lazily, on first use).
 void plan_u(const int *rp, const int *ci, IluHostPlan &hp);
-// FNV-1a over 8-byte words (bytes for the tail): the plan digests (digest
-// below, rsp_plan::digest)
-struct Fnv {
-    uint64_t h = 1469598103934665603ULL;
-    void bytes(const void *p, size_t n) {
-        const unsigned char *c = (const unsigned char *)p;
-        size_t i = 0;
-        for (; i + 8 <= n; i += 8) {
-            uint64_t w;
-            memcpy(&w, c + i, 8);
-            h = (h ^ w) * 1099511628211ULL;
-        }
-        for (; i < n; i++) h = (h ^ c[i]) * 1099511628211ULL;
-    }
-    template <typename V>
-    void vec(const hvec<V> &v) {
-        const uint64_t n = v.size();
-        bytes(&n, sizeof(n));
-        if (!v.empty()) bytes(v.data(), v.size() * sizeof(V));
-    }
-};
 // 64-bit digest (FNV-1a) of every array of the plan (tests: identical plans).
 uint64_t digest(const IluHostPlan &hp);
 
-// f(lo, hi) over [0, n) in contiguous blocks of >= grain on the analysis'
-// worker pool (also used by the SpMV planner, spmv_plan.cpp)
-void parallel_for(long long n, long long grain, const std::function<void(long long, long long)> &f);
+// ---- internal: shared by the analysis' own units (ilu_analysis.cpp,
+// ilu_plan_solve.cpp, ilu_plan_factor.cpp), not for its callers
+double now_ms();  // steady clock
+// rows grouped by level (stable: ascending row within a level)
+void group_levels(const hvec<int> &lev, int nlev, hvec<int> &ptr, hvec<int> &rows);
+// fn() timed; RSP_ILU_TIMING >= 2 prints its wall time as plan `what`
+void timed_plan(int n, const char *what, const std::function<void()> &fn);
+// fma-chain batch for a mean chain length of total / count
+inline int chain_batch(long long total, long long count) {
+    const double mean = count > 0 ? (double)total / (double)count : 0.0;
+    return mean <= 2.5 ? 2 : (mean <= 5.0 ? 4 : 8);
+}
 
 }  // namespace rsp_an
 

@@ -3,15 +3,15 @@
 // GPU/ilu0.cu:196-217): pattern validation, diagonal positions, the
 // structural-zero min-reduce, and the symbolic factor (every position's
 // update list, the intra-row stages, the stage order of each row's lower
-// positions, the divisor positions). What stays on the host (ilu_analysis.cpp)
-// is what is sequential along the dependency chains: the level sets (a row's
-// level needs its producers' levels: longest paths of the DAG, one O(nnz)
-// pass) and the greedy chunking of the launch plans.
+// positions, the divisor positions). What stays on the host (ilu_analysis.cpp,
+// ilu_plan_solve.cpp, ilu_plan_factor.cpp) is what is sequential along the
+// dependency chains: the level sets (a row's level needs its producers':
+// longest paths of the DAG, one O(nnz) pass) and the launch plans' chunking.
 //
 // Update lists: position t = (i, j) receives the pair (p = (i, k), q = (k, j))
 // for every lower position p of row i with k < j and j in row k's upper part,
 // in ascending k — the same lists, in the same order, as the host's
-// ilu_symbolic (count pass, exclusive scan, fill pass over the identical
+// symbolic_row (count pass, exclusive scan, fill pass over the identical
 // traversal; see an_pairs). Bitwise-equal plans are asserted through
 // rsp_ilu0_plan_digest against rsp_ilu0_analysis_host.
 //
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kAnThreads) void an_rows(int n, const int *__restri
 // t, count (FILL = 0) or append (p, q) to t's list (FILL = 1). A row's
 // per-position counters / cursors live in LDS (LDS_CAP entries; the wave's
 // LDS accesses are in order, and the lanes of one step hit distinct columns),
-// so every list comes out in ascending k, exactly as the host's ilu_symbolic.
+// so every list comes out in ascending k, exactly as the host's symbolic_row.
 // Rows longer than any LDS class (LDS_CAP = 0) use global cursors advanced by
 // atomics, each step waited for before the next.
 template <bool FILL, int LDS_CAP>
@@ -579,10 +579,10 @@ hipError_t ilu_an_gather_pairs(const int *rows, int nrows, const int *rp, const 
 }
 
 // ------------------------------------------------ solve plans: per-term half
-// (ilu_analysis.cpp solve_plan_terms restated; see SolveTermsArgs)
+// (ilu_plan_solve.cpp solve_plan_terms restated; see SolveTermsArgs)
 namespace {
 
-// a row's padded terms and the offset of its late terms (ilu_analysis.cpp
+// a row's padded terms and the offset of its late terms (ilu_plan_solve.cpp
 // split_padded / late_offset restated)
 __device__ __forceinline__ int st_split_padded(int ne, int cnt, int g) {
     const int pe = (ne + g - 1) / g * g, pl = (cnt - ne + g - 1) / g * g;

@@ -743,7 +743,7 @@ hipError_t ilu_an_fill(const int *const rows_c[3], const int n_c[3], int cap0, c
 hipError_t ilu_an_stages(int n, int maxlen, const int *rp, const int *ci, const int *dpos, const int *hasdiag,
                          const int *ptr, const int *upd_l, int *stage, int *lord, int *lend, int *udiv,
                          int *scratch, const int *wrows, int nwrows, hipStream_t s);
-// The per-term half of a solve plan (ilu_analysis.cpp solve_plan_terms, same
+// The per-term half of a solve plan (ilu_plan_solve.cpp solve_plan_terms, same
 // arrays bit for bit) from its per-row half already on the device: flat term
 // positions and y sources, the thin runs' window remap, row records, y
 // indices, staged terms and the chunks' staged ranges. Row i's terms, in the
@@ -759,7 +759,7 @@ struct SolveTermsArgs {
     const int *rp, *ci, *dpos;
     const int *ltp, *lts, *ltc;
     const int *lpos;  // kind 0: the split term order (position of term o of row i at lpos[rp[i] + o])
-    const int *ne;    // per row: its early terms (split order; ilu_analysis.cpp split_padded)
+    const int *ne;    // per row: its early terms (split order; ilu_plan_solve.cpp split_padded)
     rsp::LevelChunk *chunks;
     const int *cbase;  // per chunk: its thin run's first slot
     int *tpos, *src, *sid;

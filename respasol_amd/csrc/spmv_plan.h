@@ -12,7 +12,7 @@
 #include <stdint.h>
 
 #include "rsp.h"
-#include "ilu_analysis.h"
+#include "host_pool.h"
 #include "rsp_kernels.h"
 
 namespace rsp_plan {
