@@ -13,50 +13,29 @@
 
 using namespace rsp_api;
 
-// Everything an analysis left on the device (and its planning thread): the
-// info is as rsp_create_ilu0_info made it, ready for another analysis.
-static void ilu_free_device(rsp_ilu0_info *f) {
-    f->solves_task.reset();  // (joins a solve planning still running)
-    f->solves_ready = false;
-    if (f->d_arena_s) (void)hipFree(f->d_arena_s);
-    f->d_arena_s = nullptr;
-    // every array except the slot layout lives in the arenas
-    if (f->d_arena) (void)hipFree(f->d_arena);
-    if (f->d_arena_u) (void)hipFree(f->d_arena_u);
-    if (f->d_arena_sym) (void)hipFree(f->d_arena_sym);
-    if (f->d_arena_pairs) (void)hipFree(f->d_arena_pairs);
-    f->d_arena_sym = f->d_arena_pairs = nullptr;
-    if (f->d_fslots) (void)hipFree(f->d_fslots);
-    if (f->d_fbackup) (void)hipFree(f->d_fbackup);
-    f->d_fbackup = nullptr;
-    f->fbackup_bytes = 0;
-    f->last_fac = rsp_ilu0_info::FacCall();
-    for (rsp_ilu0_info::SolveCall &c : f->last_solve) c = rsp_ilu0_info::SolveCall();
-    f->d_arena = f->d_arena_u = nullptr;
-    f->d_usval = nullptr;
-    f->d_fslots = nullptr;
-    f->d_dpos = f->d_hasdiag = f->d_zero = f->d_fdone = nullptr;
-    f->d_tk = nullptr;
-    f->d_upd_ptr = f->d_upd_l = f->d_upd_u = f->d_lord = f->d_lend = f->d_udiv = nullptr;
-    f->d_sval = f->d_sx = f->d_sdg = nullptr;
-    f->fslev.clear();
-    f->fruns.clear();
-    f->d_ffitems = nullptr;
-    f->d_forig = nullptr;
-    f->d_frow = nullptr;
-    f->d_rchunks = nullptr;
-    f->d_ritems = nullptr;
-    f->d_rpairs = f->d_rstaged = f->d_rrounds = nullptr;
-    for (rsp_ilu0_info::Dag *d : {&f->L, &f->LT, &f->U, &f->F}) *d = rsp_ilu0_info::Dag();
-    f->Lb = rsp_ilu0_info::BlkDag();
-    f->LTb = rsp_ilu0_info::BlkDag();
-    f->fac_one = f->fac_scale = false;
-}
+using Dag = rsp_ilu0_info::Dag;
 
-// Device helpers of the ILU analysis upload. Many arrays in ONE device allocation: add() records each array (host data
-// to copy, or space only), commit() makes one hipMalloc and one copy per
-// array. (One allocation per array — ~40 per analysis — had cost more than
-// the copies themselves.)
+// Sub-phase wall times on stderr, for RSP_ILU_TIMING >= 3 (diagnostics).
+struct Stopwatch {
+    const char *fmt;  // (n, what, ms)
+    int n;
+    bool on = env_int("RSP_ILU_TIMING", 0) >= 3;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void operator()(const char *what) {
+        if (!on) return;
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, fmt, n, what, std::chrono::duration<double, std::milli>(t - last).count());
+        last = t;
+    }
+};
+
+// Device helper of the ILU analysis upload. Many arrays in ONE device
+// allocation: add() records each array (host data to copy, or space only),
+// commit() makes one hipMalloc and one copy per array. (One allocation per
+// array — ~40 per analysis — had cost more than the copies themselves.)
+// The arena keeps the ADDRESS of every destination pointer until commit()
+// writes it: a destination (a member of the info's rsp_ilu0_info, built in place,
+// or a local) must not move or die between its add and the commit.
 struct Arena {
     struct Item {
         void **dst;
@@ -70,18 +49,25 @@ struct Arena {
         total += (bytes + 255) & ~(size_t)255;
     }
     template <typename V>
-    void up(V **dst, const rsp_an::hvec<V> &v) {
+    void up(const V **dst, const rsp_an::hvec<V> &v) {  // (a kernel-argument struct's read-only array)
         add((void **)dst, v.empty() ? nullptr : v.data(), std::max<size_t>(v.size(), 1) * sizeof(V),
             v.size() * sizeof(V));
     }
-    void space(void **dst, size_t bytes) { add(dst, nullptr, bytes, 0); }
-    hipError_t commit(void **base, hipStream_t s) {
-        *base = nullptr;
+    template <typename V>
+    void up(V **dst, const rsp_an::hvec<V> &v) {
+        up((const V **)dst, v);
+    }
+    template <typename T>  // (T: any element type, const or not, or void)
+    void space(T **dst, size_t bytes) {
+        add((void **)dst, nullptr, bytes, 0);
+    }
+    hipError_t commit(DevMem &base, hipStream_t s) {
+        base = DevMem();
         if (total == 0) return hipSuccess;
-        hipError_t e = hipMalloc(base, total);
+        hipError_t e = hipMalloc(&base.p, total);
         if (e != hipSuccess) return e;
         for (const Item &it : items) {
-            *it.dst = (char *)*base + it.off;
+            *it.dst = (char *)base.p + it.off;
             if (it.copy && e == hipSuccess)
                 e = hipMemcpyAsync(*it.dst, it.src, it.copy, hipMemcpyHostToDevice, s);
         }
@@ -90,8 +76,9 @@ struct Arena {
     }
 };
 
-// Upload one DAG's solve plan (into the arena `ar`) and keep its host parts.
-static void dag_upload(Arena &ar, rsp_ilu0_info::Dag &d, const rsp_an::DagHost &h) {
+// What dag_upload and dag_upload_rows share: the DAG's host parts and the
+// first arrays of its plan.
+static void dag_upload_head(Arena &ar, Dag &d, const rsp_an::DagHost &h, int nterms) {
     d.ptr = h.ptr;
     d.batch = h.batch;
     d.group = h.group;
@@ -99,78 +86,69 @@ static void dag_upload(Arena &ar, rsp_ilu0_info::Dag &d, const rsp_an::DagHost &
     d.nshort = h.sp.nshort;
     d.nwave = h.sp.nwave;
     d.sbase = h.sp.sbase;
-    d.nterms = (int)h.sp.tpos.size();
-    if (!d.d_rows) {  // (L's levels may be in the factor's arena already)
-        ar.up(&d.d_rows, h.rows);
-        ar.up(&d.d_ptr, h.ptr);
+    d.nterms = nterms;
+    if (!d.plan.rows) {  // (L's levels may be in the factor's arena already)
+        ar.up(&d.plan.rows, h.rows);
+        ar.up(&d.plan.ptr_dev, h.ptr);
     }
-    ar.up(&d.d_tasks, h.sp.tasks);
-    ar.up(&d.d_nshort, h.sp.nshort);
-    ar.up(&d.d_tpos, h.sp.tpos);
-    ar.up(&d.d_src, h.sp.src);
-    ar.up(&d.d_chunks, h.sp.chunks);
-    ar.up(&d.d_trow, h.sp.trow);
-    ar.up(&d.d_sid, h.sp.sid);
-    ar.up(&d.d_stg, h.sp.stg);
-    ar.up(&d.d_fitems, h.sp.fitems);
+    ar.up(&d.plan.tasks, h.sp.tasks);
+    ar.up(&d.plan.nshort, h.sp.nshort);
+}
+
+// Upload one DAG's solve plan (into the arena `ar`) and keep its host parts.
+static void dag_upload(Arena &ar, Dag &d, const rsp_an::DagHost &h) {
+    dag_upload_head(ar, d, h, (int)h.sp.tpos.size());
+    ar.up(&d.plan.tpos, h.sp.tpos);
+    ar.up(&d.plan.src, h.sp.src);
+    ar.up(&d.plan.chunks, h.sp.chunks);
+    ar.up(&d.plan.trow, h.sp.trow);
+    ar.up(&d.plan.sid, h.sp.sid);
+    ar.up(&d.plan.stg, h.sp.stg);
+    ar.up(&d.plan.fitems, h.sp.fitems);
 }
 
 // Upload a block-inverse solve plan (into the arena) with its scratch.
 static void blk_upload(Arena &ar, rsp_ilu0_info::BlkDag &d, const rsp_an::BlkPlanHost &h) {
+    rsp::BlkArgs &b = d.args;
     d.on = true;
-    d.nb = h.nb;
-    d.lds_elems = h.lds_elems;
-    d.lds_words = h.lds_words;
-    d.entries = h.entries;
-    d.nlong = h.nlong;
     d.segs = h.segs;
-    ar.up(&d.d_order, h.order);
-    ar.up(&d.d_desc, h.desc);
-    ar.up(&d.d_rows, h.rows);
-    ar.up(&d.d_ref, h.ref);
-    ar.up(&d.d_vpos, h.vpos);
-    ar.up(&d.d_eord, h.eord);
-    ar.up(&d.d_lptr, h.lptr);
-    ar.up(&d.d_rptr, h.rptr);
-    ar.up(&d.d_rit, h.rit);
-    ar.space(&d.d_ev, ((size_t)h.entries + 1) * sizeof(double));
-    ar.space(&d.d_yp, ((size_t)h.n + 1) * sizeof(double));  // (+ a spare cell, trsv_blk_seg)
-    ar.space(&d.d_rc, (size_t)h.nb * 64 * 144);
+    b.n = h.n;
+    b.nb = h.nb;
+    b.lds_elems = h.lds_elems;
+    b.lds_words = h.lds_words;
+    ar.up(&b.order, h.order);
+    ar.up(&b.desc, h.desc);
+    ar.up(&b.rows, h.rows);
+    ar.up(&b.ref, h.ref);
+    ar.up(&b.vpos, h.vpos);
+    ar.up(&b.eord, h.eord);
+    ar.up(&b.lptr, h.lptr);
+    ar.up(&b.rptr, h.rptr);
+    ar.up(&b.rit, h.rit);
+    ar.space(&b.ev, ((size_t)h.entries + 1) * sizeof(double));
+    ar.space(&b.yp, ((size_t)h.n + 1) * sizeof(double));  // (+ a spare cell, trsv_blk_seg)
+    ar.space(&b.rc, (size_t)h.nb * 64 * 144);
 }
 
 // Upload one DAG's per-row solve plan (L or L^T) into the arena and reserve
 // the per-term arrays, which rsp_k::ilu_an_solve_terms then builds on the
 // device (t: its arguments; pointers set at commit, the rest by the caller).
-static void dag_upload_rows(Arena &ar, rsp_ilu0_info::Dag &d, const rsp_an::DagHost &h, int n,
-                            rsp_k::SolveTermsArgs &t) {
-    d.ptr = h.ptr;
-    d.batch = h.batch;
-    d.group = h.group;
-    d.segs = h.sp.segs;
-    d.nshort = h.sp.nshort;
-    d.nwave = h.sp.nwave;
-    d.sbase = h.sp.sbase;
-    d.nterms = std::max(h.sp.nterm, 1);
+static void dag_upload_rows(Arena &ar, Dag &d, const rsp_an::DagHost &h, int n, rsp_k::SolveTermsArgs &t) {
+    dag_upload_head(ar, d, h, std::max(h.sp.nterm, 1));
     const size_t nx = h.rows.size(), nch = h.sp.chunks.size();
     long long thin_terms = 0;
     for (const rsp::LevelChunk &ch : h.sp.chunks) thin_terms += ch.k1 - ch.k0;
-    if (!d.d_rows) {  // (L's levels may be in the factor's arena already)
-        ar.up(&d.d_rows, h.rows);
-        ar.up(&d.d_ptr, h.ptr);
-    }
-    ar.up(&d.d_tasks, h.sp.tasks);
-    ar.up(&d.d_nshort, h.sp.nshort);
-    ar.space((void **)&d.d_tpos, (size_t)d.nterms * 4);
-    ar.space((void **)&d.d_src, (size_t)d.nterms * 4);
-    ar.space((void **)&d.d_sid, (size_t)d.nterms * 4);
-    ar.up(&d.d_chunks, h.sp.chunks);  // staged ranges written on the device
-    ar.space((void **)&d.d_trow, std::max<size_t>(nx, 1) * sizeof(rsp::ThinRowPlan));
-    ar.space((void **)&d.d_stg, (size_t)std::max(thin_terms, 1LL) * sizeof(rsp::StagedTerm));
-    ar.up(&d.d_fitems, h.sp.fitems);
-    ar.up((int **)&t.cbase, h.sp.cbase);
-    ar.space((void **)&t.slot_of, (size_t)std::max(n, 1) * 4);
-    ar.space((void **)&t.nst, (nch + 1) * 4);
-    ar.space((void **)&t.nst_ptr, (nch + 1) * 4);
+    ar.space(&d.plan.tpos, (size_t)d.nterms * 4);
+    ar.space(&d.plan.src, (size_t)d.nterms * 4);
+    ar.space(&d.plan.sid, (size_t)d.nterms * 4);
+    ar.up(&d.plan.chunks, h.sp.chunks);  // staged ranges written on the device
+    ar.space(&d.plan.trow, std::max<size_t>(nx, 1) * sizeof(rsp::ThinRowPlan));
+    ar.space(&d.plan.stg, (size_t)std::max(thin_terms, 1LL) * sizeof(rsp::StagedTerm));
+    ar.up(&d.plan.fitems, h.sp.fitems);
+    ar.up(&t.cbase, h.sp.cbase);
+    ar.space(&t.slot_of, (size_t)std::max(n, 1) * 4);
+    ar.space(&t.nst, (nch + 1) * 4);
+    ar.space(&t.nst_ptr, (nch + 1) * 4);
     size_t tb = 0;
     (void)rsp_k::ilu_an_scan(nullptr, nullptr, (int)nch + 1, nullptr, &tb, nullptr);
     ar.space(&t.scan, std::max<size_t>(tb, 16));
@@ -181,23 +159,25 @@ static void dag_upload_rows(Arena &ar, rsp_ilu0_info::Dag &d, const rsp_an::DagH
     t.group = h.group;
 }
 
-// After the commit: the per-term arrays of a DAG uploaded by dag_upload_rows.
-static hipError_t dag_build_terms(rsp_ilu0_info::Dag &d, rsp_k::SolveTermsArgs &t, hipStream_t s) {
-    t.tasks = d.d_tasks;
-    t.ptr = d.d_ptr;
-    t.chunks = d.d_chunks;
-    t.tpos = d.d_tpos;
-    t.src = d.d_src;
-    t.sid = d.d_sid;
-    t.trow = d.d_trow;
-    t.stg = d.d_stg;
+// After the commit: the per-term arrays of a DAG uploaded by dag_upload_rows
+// (the one place that writes through the plan's read-only pointers).
+static hipError_t dag_build_terms(const Dag &d, rsp_k::SolveTermsArgs &t, hipStream_t s) {
+    const rsp::LevelPlan &p = d.plan;
+    t.tasks = p.tasks;
+    t.ptr = p.ptr_dev;
+    t.chunks = const_cast<rsp::LevelChunk *>(p.chunks);
+    t.tpos = const_cast<int *>(p.tpos);
+    t.src = const_cast<int *>(p.src);
+    t.sid = const_cast<int *>(p.sid);
+    t.trow = const_cast<rsp::ThinRowPlan *>(p.trow);
+    t.stg = const_cast<rsp::StagedTerm *>(p.stg);
     return rsp_k::ilu_an_solve_terms(t, s);
 }
 
 // Tests only (RSP_ILU_DIGEST): the device-built per-term arrays back into the
 // host plan, so the digest covers them.
-static hipError_t dag_download_terms(const rsp_ilu0_info::Dag &d, const rsp_k::SolveTermsArgs &t,
-                                     rsp_an::DagHost &h, hipStream_t s) {
+static hipError_t dag_download_terms(const Dag &d, const rsp_k::SolveTermsArgs &t, rsp_an::DagHost &h,
+                                     hipStream_t s) {
     rsp_an::SolvePlan &sp = h.sp;
     int nstg = 0;
     hipError_t e = hipMemcpyAsync(&nstg, t.nst_ptr + t.nch, 4, hipMemcpyDeviceToHost, s);
@@ -208,15 +188,15 @@ static hipError_t dag_download_terms(const rsp_ilu0_info::Dag &d, const rsp_k::S
     sp.sid.resize((size_t)d.nterms);
     sp.trow.resize(std::max<size_t>((size_t)t.nx, 1));
     sp.stg.resize((size_t)std::max(nstg, 1));
-    e = hipMemcpyAsync(sp.tpos.data(), d.d_tpos, sp.tpos.size() * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(sp.src.data(), d.d_src, sp.src.size() * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(sp.sid.data(), d.d_sid, sp.sid.size() * 4, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(sp.tpos.data(), t.tpos, sp.tpos.size() * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sp.src.data(), t.src, sp.src.size() * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sp.sid.data(), t.sid, sp.sid.size() * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(sp.trow.data(), d.d_trow, sp.trow.size() * sizeof(rsp::ThinRowPlan), hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(sp.trow.data(), t.trow, sp.trow.size() * sizeof(rsp::ThinRowPlan), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(sp.stg.data(), d.d_stg, sp.stg.size() * sizeof(rsp::StagedTerm), hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(sp.stg.data(), t.stg, sp.stg.size() * sizeof(rsp::StagedTerm), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(sp.chunks.data(), d.d_chunks, sp.chunks.size() * sizeof(rsp::LevelChunk),
+        e = hipMemcpyAsync(sp.chunks.data(), t.chunks, sp.chunks.size() * sizeof(rsp::LevelChunk),
                            hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
@@ -252,15 +232,7 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
                                         rsp_an::Phases &ph, const std::function<void()> &after_levels) {
     const int n = hp.n, nnz_s = hp.nnz_s;
     hipStream_t s = h->stream;
-    const bool tm3 = env_int("RSP_ILU_TIMING", 0) >= 3;  // diagnostics: sub-phase wall times
-    auto t_last = std::chrono::steady_clock::now();
-    auto sub = [&](const char *what) {
-        if (!tm3) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "rsp_ilu0_analysis n=%d     %-22s %8.2f ms\n", n, what,
-                std::chrono::duration<double, std::milli>(t - t_last).count());
-        t_last = t;
-    };
+    Stopwatch sub{"rsp_ilu0_analysis n=%d     %-22s %8.2f ms\n", n};
     rsp_an::hvec<int> dev_rows, long_rows, wave_rows;
     const int wave_row = (int)env_int("RSP_AN_WAVE_ROW", kAnWaveRow);
     int cap0 = 1;  // the longest device row: the pair kernel's LDS per row
@@ -330,29 +302,35 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
     RSP_CHECK_HIP(rsp_k::ilu_an_scan(nullptr, nullptr, nnz_s + 1, nullptr, &scan_bytes, s));
     Arena ar;
     int *d_flags = nullptr, *d_cnt = nullptr, *d_stage = nullptr, *d_scratch = nullptr, *d_rows = nullptr;
+    // the symbolic arrays the kernels below write and the factor reads (f->fac)
+    int *d_dpos = nullptr, *d_hasdiag = nullptr, *d_upd_ptr = nullptr, *d_upd_l = nullptr, *d_upd_u = nullptr;
+    int *d_lord = nullptr, *d_lend = nullptr, *d_udiv = nullptr;
     void *d_scan = nullptr;
-    ar.space((void **)&f->d_dpos, (size_t)std::max(n, 1) * 4);
-    ar.space((void **)&f->d_hasdiag, (size_t)std::max(n, 1) * 4);
-    ar.space((void **)&d_flags, 2 * 4);
-    ar.space((void **)&d_cnt, ((size_t)nnz_s + 1) * 4);
-    ar.space((void **)&f->d_upd_ptr, ((size_t)nnz_s + 1) * 4);
-    ar.space((void **)&d_stage, (size_t)std::max(nnz_s, 1) * 4);
-    ar.space((void **)&f->d_lord, (size_t)std::max(nnz_s, 1) * 4);
-    ar.space((void **)&f->d_lend, (size_t)std::max(nnz_s, 1) * 4);
-    ar.space((void **)&f->d_udiv, (size_t)std::max(nnz_s, 1) * 4);
-    ar.space((void **)&d_scratch, (size_t)std::max(nnz_s, 1) * 4);
+    ar.space(&d_dpos, (size_t)std::max(n, 1) * 4);
+    ar.space(&d_hasdiag, (size_t)std::max(n, 1) * 4);
+    ar.space(&d_flags, 2 * 4);
+    ar.space(&d_cnt, ((size_t)nnz_s + 1) * 4);
+    ar.space(&d_upd_ptr, ((size_t)nnz_s + 1) * 4);
+    ar.space(&d_stage, (size_t)std::max(nnz_s, 1) * 4);
+    ar.space(&d_lord, (size_t)std::max(nnz_s, 1) * 4);
+    ar.space(&d_lend, (size_t)std::max(nnz_s, 1) * 4);
+    ar.space(&d_udiv, (size_t)std::max(nnz_s, 1) * 4);
+    ar.space(&d_scratch, (size_t)std::max(nnz_s, 1) * 4);
     ar.space(&d_scan, std::max<size_t>(scan_bytes, 16));
     ar.up(&d_rows, dev_rows);
     int *d_wrows = nullptr;
     ar.up(&d_wrows, wave_rows);
     sub("arena");
-    RSP_CHECK_HIP(ar.commit(&f->d_arena_sym, s));
+    RSP_CHECK_HIP(ar.commit(f->arena_sym, s));
+    rsp::IluArgs &fa = f->fac;
+    fa.dpos = d_dpos, fa.hasdiag = d_hasdiag, fa.upd_ptr = d_upd_ptr;
+    fa.lord = d_lord, fa.lend = d_lend, fa.udiv = d_udiv;
     // the device's diagonal positions and flags (its validation flags are not
     // read: the host check above gave the same verdict)
-    RSP_CHECK_HIP(rsp_k::ilu_an_rows(n, d_rp, d_ci, f->d_dpos, f->d_hasdiag, d_flags, s));
+    RSP_CHECK_HIP(rsp_k::ilu_an_rows(n, d_rp, d_ci, d_dpos, d_hasdiag, d_flags, s));
     const int n_c[3] = {(int)dev_rows.size(), 0, 0};
     const int *rows_c[3] = {d_rows, nullptr, nullptr};
-    RSP_CHECK_HIP(rsp_k::ilu_an_count(rows_c, n_c, cap0, d_rp, d_ci, f->d_dpos, f->d_hasdiag, d_cnt, d_scratch, s));
+    RSP_CHECK_HIP(rsp_k::ilu_an_count(rows_c, n_c, cap0, d_rp, d_ci, d_dpos, d_hasdiag, d_cnt, d_scratch, s));
     sub("rows + count kernels");
     // the long rows' counts on the host
     rsp_an::hvec<int> hcnt(long_rows.empty() ? 0 : (size_t)nnz_s);
@@ -363,9 +341,9 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
                                      (size_t)(rp[(size_t)i + 1] - rp[(size_t)i]) * 4, hipMemcpyHostToDevice, s));
     sub("long-row counts");
     RSP_CHECK_HIP(hipMemsetAsync(d_cnt + nnz_s, 0, 4, s));
-    RSP_CHECK_HIP(rsp_k::ilu_an_scan(d_cnt, f->d_upd_ptr, nnz_s + 1, d_scan, &scan_bytes, s));
+    RSP_CHECK_HIP(rsp_k::ilu_an_scan(d_cnt, d_upd_ptr, nnz_s + 1, d_scan, &scan_bytes, s));
     rsp_an::resize_uninit(hp.sym.upd_ptr, (size_t)nnz_s + 1);
-    RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_ptr.data(), f->d_upd_ptr, ((size_t)nnz_s + 1) * 4,
+    RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_ptr.data(), d_upd_ptr, ((size_t)nnz_s + 1) * 4,
                                  hipMemcpyDeviceToHost, s));
     RSP_CHECK_HIP(hipStreamSynchronize(s));
     sub("scan + D2H upd_ptr");
@@ -374,14 +352,15 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
     const int total = hp.sym.upd_ptr[(size_t)nnz_s];
     if (total < 0) return RSP_STATUS_ALLOC_FAILED;
     Arena ap;
-    ap.space((void **)&f->d_upd_l, (size_t)std::max(total, 1) * 4);
-    ap.space((void **)&f->d_upd_u, (size_t)std::max(total, 1) * 4);
-    RSP_CHECK_HIP(ap.commit(&f->d_arena_pairs, s));
+    ap.space(&d_upd_l, (size_t)std::max(total, 1) * 4);
+    ap.space(&d_upd_u, (size_t)std::max(total, 1) * 4);
+    RSP_CHECK_HIP(ap.commit(f->arena_pairs, s));
+    fa.upd_l = d_upd_l, fa.upd_u = d_upd_u;
     sub("pairs arena");
-    RSP_CHECK_HIP(rsp_k::ilu_an_fill(rows_c, n_c, cap0, d_rp, d_ci, f->d_dpos, f->d_hasdiag, f->d_upd_ptr, d_scratch,
-                                     f->d_upd_l, f->d_upd_u, s));
-    RSP_CHECK_HIP(rsp_k::ilu_an_stages(n, std::min(wave_row, kAnDevRow), d_rp, d_ci, f->d_dpos, f->d_hasdiag, f->d_upd_ptr, f->d_upd_l,
-                                       d_stage, f->d_lord, f->d_lend, f->d_udiv, d_scratch, d_wrows,
+    RSP_CHECK_HIP(rsp_k::ilu_an_fill(rows_c, n_c, cap0, d_rp, d_ci, d_dpos, d_hasdiag, d_upd_ptr, d_scratch,
+                                     d_upd_l, d_upd_u, s));
+    RSP_CHECK_HIP(rsp_k::ilu_an_stages(n, std::min(wave_row, kAnDevRow), d_rp, d_ci, d_dpos, d_hasdiag, d_upd_ptr, d_upd_l,
+                                       d_stage, d_lord, d_lend, d_udiv, d_scratch, d_wrows,
                                        (int)wave_rows.size(), s));
     // the level sets (host thread, started above) while the device fills the update lists
     levels.join();
@@ -410,26 +389,25 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
         if (packed > 0) {
             Arena ag;
             int *d_trows = nullptr, *d_cbase = nullptr, *d_pl = nullptr, *d_pu = nullptr;
-            void *d_gather = nullptr;
+            DevMem gather;
             ag.up(&d_trows, trows);
             ag.up(&d_cbase, cbase);
-            ag.space((void **)&d_pl, (size_t)packed * 4);
-            ag.space((void **)&d_pu, (size_t)packed * 4);
-            RSP_CHECK_HIP(ag.commit(&d_gather, s));
-            hipError_t e = rsp_k::ilu_an_gather_pairs(d_trows, (int)trows.size(), d_rp, f->d_upd_ptr, d_cbase,
-                                                      f->d_upd_l, f->d_upd_u, d_pl, d_pu, s);
+            ag.space(&d_pl, (size_t)packed * 4);
+            ag.space(&d_pu, (size_t)packed * 4);
+            RSP_CHECK_HIP(ag.commit(gather, s));
+            hipError_t e = rsp_k::ilu_an_gather_pairs(d_trows, (int)trows.size(), d_rp, d_upd_ptr, d_cbase,
+                                                      d_upd_l, d_upd_u, d_pl, d_pu, s);
             if (e == hipSuccess) e = hipMemcpyAsync(hp.sym.upd_l.data(), d_pl, (size_t)packed * 4, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipMemcpyAsync(hp.sym.upd_u.data(), d_pu, (size_t)packed * 4, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            (void)hipFree(d_gather);
             RSP_CHECK_HIP(e);
         }
     } else {
         rsp_an::resize_uninit(hp.sym.upd_l, (size_t)total);
         rsp_an::resize_uninit(hp.sym.upd_u, (size_t)total);
         if (total > 0) {
-            RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_l.data(), f->d_upd_l, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-            RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_u.data(), f->d_upd_u, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+            RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_l.data(), d_upd_l, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+            RSP_CHECK_HIP(hipMemcpyAsync(hp.sym.upd_u.data(), d_upd_u, (size_t)total * 4, hipMemcpyDeviceToHost, s));
         }
     }
     rsp_an::resize_uninit(hp.sym.stage, want_stage ? (size_t)nnz_s : 0);
@@ -446,12 +424,12 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
             const size_t rs = (size_t)rp[(size_t)i], len = (size_t)(rp[(size_t)i + 1] - rp[(size_t)i]);
             const size_t q0 = (size_t)hp.sym.upd_ptr[rs], nq = (size_t)hp.sym.upd_ptr[rs + len] - q0;
             if (nq > 0) {
-                RSP_CHECK_HIP(hipMemcpyAsync(f->d_upd_l + q0, hp.sym.upd_l.data() + q0, nq * 4, hipMemcpyHostToDevice, s));
-                RSP_CHECK_HIP(hipMemcpyAsync(f->d_upd_u + q0, hp.sym.upd_u.data() + q0, nq * 4, hipMemcpyHostToDevice, s));
+                RSP_CHECK_HIP(hipMemcpyAsync(d_upd_l + q0, hp.sym.upd_l.data() + q0, nq * 4, hipMemcpyHostToDevice, s));
+                RSP_CHECK_HIP(hipMemcpyAsync(d_upd_u + q0, hp.sym.upd_u.data() + q0, nq * 4, hipMemcpyHostToDevice, s));
             }
-            RSP_CHECK_HIP(hipMemcpyAsync(f->d_lord + rs, lord.data() + rs, len * 4, hipMemcpyHostToDevice, s));
-            RSP_CHECK_HIP(hipMemcpyAsync(f->d_lend + rs, lend.data() + rs, len * 4, hipMemcpyHostToDevice, s));
-            RSP_CHECK_HIP(hipMemcpyAsync(f->d_udiv + rs, udiv.data() + rs, len * 4, hipMemcpyHostToDevice, s));
+            RSP_CHECK_HIP(hipMemcpyAsync(d_lord + rs, lord.data() + rs, len * 4, hipMemcpyHostToDevice, s));
+            RSP_CHECK_HIP(hipMemcpyAsync(d_lend + rs, lend.data() + rs, len * 4, hipMemcpyHostToDevice, s));
+            RSP_CHECK_HIP(hipMemcpyAsync(d_udiv + rs, udiv.data() + rs, len * 4, hipMemcpyHostToDevice, s));
         }
         RSP_CHECK_HIP(hipStreamSynchronize(s));
     }
@@ -461,7 +439,7 @@ static rsp_status_t ilu_symbolic_device(rsp_handle_t h, rsp_ilu0_info *f, const 
 }
 
 static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_row_offsets,
-                                  const int *d_col_ind, rsp_ilu0_info_t f) {
+                                  const int *d_col_ind, rsp_ilu0_info *f) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     // diagnostics: RSP_ILU_TIMING=1 prints the wall time of each analysis phase
     rsp_an::Phases ph;
@@ -469,21 +447,9 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
     ph.n = n;
     ph.start();
     if (!f || n < 0 || nnz < 0 || (n > 0 && !d_row_offsets)) return RSP_STATUS_INVALID_VALUE;
-    const bool tm3 = env_int("RSP_ILU_TIMING", 0) >= 3;  // diagnostics: preamble sub-phases
-    auto t_pre = std::chrono::steady_clock::now();
-    auto pre = [&](const char *what) {
-        if (!tm3) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "rsp_ilu0_analysis n=%d     %-22s %8.2f ms\n", n, what,
-                std::chrono::duration<double, std::milli>(t - t_pre).count());
-        t_pre = t;
-    };
-    ilu_free_device(f);
+    Stopwatch pre{"rsp_ilu0_analysis n=%d     %-22s %8.2f ms\n", n};  // diagnostics: preamble sub-phases
+    f->reset();  // the previous analysis goes: its planning thread, device arrays, counters, call records
     pre("free");
-    f->analysed = 0;
-    f->factored = 0;
-    f->structural_zero = -1;
-    f->host.reset();
     // the pattern to the host (row offsets first: the stored entries must lie
     // inside the declared arrays before colidx is read)
     rsp_an::hvec<int> rp((size_t)n + 1, 0);
@@ -539,7 +505,7 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
     if (st == RSP_STATUS_SUCCESS) rsp_an::plan_factor(rp.data(), ci.data(), slot_cap_ints(), *hp);
     if (st != RSP_STATUS_SUCCESS) {
         solves.reset();  // (joined before the buffers it reads go)
-        ilu_free_device(f);
+        f->reset();
         return st;
     }
     // the U DAG (--true-lu extension) is planned on its first use
@@ -555,51 +521,45 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
         hp->udiv.resize((size_t)nnz_s);
         hipError_t e = hipSuccess;
         if (nnz_s > 0) {
-            e = hipMemcpyAsync(hp->sym.lord.data(), f->d_lord, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
+            e = hipMemcpyAsync(hp->sym.lord.data(), f->fac.lord, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(hp->sym.lend.data(), f->d_lend, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
+                e = hipMemcpyAsync(hp->sym.lend.data(), f->fac.lend, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(hp->udiv.data(), f->d_udiv, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
+                e = hipMemcpyAsync(hp->udiv.data(), f->fac.udiv, (size_t)nnz_s * 4, hipMemcpyDeviceToHost, h->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
         f->digest = e == hipSuccess ? 1 : 0;  // computed once the solve terms exist (below)
     }
-    // (diagnostics, RSP_ILU_TIMING >= 3: the upload's steps)
-    auto t_up = std::chrono::steady_clock::now();
-    auto up_step = [&](const char *what) {
-        if (!tm3) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "rsp_ilu0_analysis n=%d     upload: %-16s %8.2f ms\n", n, what,
-                std::chrono::duration<double, std::milli>(t - t_up).count());
-        t_up = t;
-    };
-    // everything in one device allocation
+    Stopwatch up_step{"rsp_ilu0_analysis n=%d     upload: %-16s %8.2f ms\n", n};  // diagnostics: the upload's steps
+    // everything in one device allocation; the factor's arguments (f->fac) get
+    // the pattern and the factor plan here, beside ilu_symbolic_device's arrays
+    rsp::IluArgs &fa = f->fac;
+    fa.n = n;
+    fa.rowptr = d_row_offsets;
+    fa.colidx = d_col_ind;
     Arena ar;
-    ar.up(&f->d_rchunks, hp->fplan.chunks);
-    ar.up(&f->d_ritems, hp->fplan.items);
-    ar.up(&f->d_rpairs, hp->fplan.pairs);
-    ar.up(&f->d_rstaged, hp->fplan.staged);
-    ar.up(&f->d_rrounds, hp->fplan.rounds);
-    ar.up(&f->d_frow, hp->frow);
-    ar.up(&f->d_ffitems, hp->ffitems);
+    ar.up(&fa.rchunks, hp->fplan.chunks);
+    ar.up(&fa.ritems, hp->fplan.items);
+    ar.up(&fa.rpairs, hp->fplan.pairs);
+    ar.up(&fa.rstaged, hp->fplan.staged);
+    ar.up(&fa.rrounds, hp->fplan.rounds);
+    ar.up(&fa.frow, hp->frow);
+    ar.up(&fa.fitems, hp->ffitems);
     f->fruns = hp->fruns;
-    f->fac_one = hp->fac_one;  // the factor's one level (rsp_an::IluHostPlan::F), else L's
-    f->fac_scale = hp->fac_scale;
-    if (hp->fac_one) {
-        f->F.ptr = hp->F.ptr;
-        ar.up(&f->F.d_rows, hp->F.rows);
-        ar.up(&f->F.d_ptr, hp->F.ptr);
-    } else {  // the factor walks L's levels (the solve plans add the rest of L at ilu_solves_ready)
-        f->L.ptr = hp->L.ptr;
-        ar.up(&f->L.d_rows, hp->L.rows);
-        ar.up(&f->L.d_ptr, hp->L.ptr);
-    }
+    f->fac_one = hp->fac_one;    // the factor walks its own one level (rsp_an::IluHostPlan::F), else L's
+    fa.fac_one = hp->fac_scale;  // (IluArgs' name for another thing:) the whole factor is ilu0_scale_lower
+    // (the solve plans add the rest of L at ilu_solves_ready)
+    Dag &fd = hp->fac_one ? f->F : f->L;
+    const rsp_an::DagHost &fh = hp->fac_one ? hp->F : hp->L;
+    fd.ptr = fh.ptr;
+    ar.up(&fd.plan.rows, fh.rows);
+    ar.up(&fd.plan.ptr_dev, fh.ptr);
     // flow runs: the saved upper input values of their rows (ilu0_flow_prep)
-    if (!hp->fruns.empty()) ar.space(&f->d_forig, (size_t)std::max(hp->nnz_s, 1) * sizeof(double));
-    ar.space((void **)&f->d_zero, 8 * sizeof(int));  // zero pivot, flow give-ups, claim counter
+    if (!hp->fruns.empty()) ar.space(&fa.forig, (size_t)std::max(hp->nnz_s, 1) * sizeof(double));
+    ar.space(&f->d_zero, 8 * sizeof(int));  // zero pivot, flow give-ups, claim counter
     // flow items (factor rows; solve items hold >= 1 row each, U's included) <= n
-    ar.space((void **)&f->d_fdone, (size_t)std::max(n, 1) * sizeof(int));
-    ar.space((void **)&f->d_tk, 2 * rsp::kFlowTicketCtrs * sizeof(unsigned));
+    ar.space(&f->d_fdone, (size_t)std::max(n, 1) * sizeof(int));
+    ar.space(&f->d_tk, 2 * rsp::kFlowTicketCtrs * sizeof(unsigned));
     int4 *d_desc = nullptr;
     long long *d_offs = nullptr;
     if (!hp->slot_desc.empty()) {
@@ -607,8 +567,9 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
         ar.up(&d_offs, hp->slot_offs);
     }
     up_step("arena build");
-    hipError_t e = ar.commit(&f->d_arena, h->stream);
+    hipError_t e = ar.commit(f->arena, h->stream);
     up_step("commit (H2D)");
+    fa.zero_pivot = f->d_zero;
     // on the handle's stream like everything else (the call is host-blocking:
     // the counters are in place when it returns, whatever stream comes next)
     if (e == hipSuccess) e = hipMemsetD32Async(f->d_zero, INT_MAX, 1, h->stream);
@@ -616,44 +577,31 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
     if (e == hipSuccess) e = hipMemsetD32Async(f->d_fdone, 0, (size_t)std::max(n, 1), h->stream);
     if (e == hipSuccess) e = hipMemsetD32Async(f->d_tk, 0, 2 * rsp::kFlowTicketCtrs, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    f->tk_seq = 0;
-    f->fac_gen = 0;
-    f->claim_host = 0;
-    f->flow_epoch = 0;
-    f->solve_gen[0] = f->solve_gen[1] = f->solve_gen[2] = 0;
     // fat factor slots, written on the device from the uploaded symbolic
     // arrays; the layout is an optimisation: without its memory, or if the
     // build fails, the FacRow path factors every fat level (same bits)
     if (e == hipSuccess && hp->slot_total > 0) {
-        hipError_t es = hipMalloc((void **)&f->d_fslots, (size_t)hp->slot_total * sizeof(int));
+        hipError_t es = hipMalloc(&f->fslots.p, (size_t)hp->slot_total * sizeof(int));
         if (es == hipSuccess) {
-            rsp::IluArgs a{};
-            a.n = n;
-            a.rowptr = d_row_offsets;
-            a.dpos = f->d_dpos;
-            a.hasdiag = f->d_hasdiag;
-            a.upd_ptr = f->d_upd_ptr;
-            a.upd_l = f->d_upd_l;
-            a.upd_u = f->d_upd_u;
-            a.lord = f->d_lord;
-            a.lend = f->d_lend;
-            a.udiv = f->d_udiv;
-            a.plan.rows = f->fdag().d_rows;
-            es = rsp_k::ilu0_build_slots(a, d_desc, d_offs, (int)hp->slot_desc.size(), f->d_fslots, h->stream);
+            rsp::IluArgs a = fa;  // (its plan is all zero: fac is value-initialised, the plan set per call)
+            a.plan.rows = fd.plan.rows;
+            es = rsp_k::ilu0_build_slots(a, d_desc, d_offs, (int)hp->slot_desc.size(), (int *)f->fslots.p,
+                                         h->stream);
             if (es == hipSuccess) es = hipStreamSynchronize(h->stream);
         }
         up_step("factor slots");
-        if (es != hipSuccess) {
+        if (es == hipSuccess) {
+            fa.fslots = (const int *)f->fslots.p;
+        } else {
             (void)hipGetLastError();
-            if (f->d_fslots) (void)hipFree(f->d_fslots);
-            f->d_fslots = nullptr;
+            f->fslots = DevMem();
             f->fslev.assign(f->fslev.size(), rsp::FacSlotLevel{0, 0, 0, 0, 0});
             f->fruns.clear();  // the flow runs read the slots too
         }
     }
     ph.mark("upload");
     if (e != hipSuccess) {
-        ilu_free_device(f);
+        f->reset();
         return e == hipErrorOutOfMemory ? RSP_STATUS_ALLOC_FAILED : RSP_STATUS_EXECUTION_FAILED;
     }
     // (the buffers keep their addresses: the solve plans' thread reads them on)
@@ -665,8 +613,6 @@ static rsp_status_t ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_r
     f->han = h;
     f->n = n;
     f->nnz_s = nnz_s;
-    f->rowptr = d_row_offsets;
-    f->colidx = d_col_ind;
     f->analysed = 1;
     return RSP_STATUS_SUCCESS;
 }
@@ -690,35 +636,26 @@ rsp_status_t rsp_api::ilu_solves_ready(rsp_handle_t h, rsp_ilu0_info *f) {
     rsp_an::IluHostPlan *hp = f->host.get();
     const int n = f->n;
     const bool dev_terms = f->dev_terms;
-    const int *d_row_offsets = f->rowptr, *d_col_ind = f->colidx;
-    const bool tm3 = env_int("RSP_ILU_TIMING", 0) >= 3;  // diagnostics
-    auto t_up = std::chrono::steady_clock::now();
-    auto up_step = [&](const char *what) {
-        if (!tm3) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "rsp_trsv_analysis n=%d     upload: %-16s %8.2f ms\n", n, what,
-                std::chrono::duration<double, std::milli>(t - t_up).count());
-        t_up = t;
-    };
+    Stopwatch up_step{"rsp_trsv_analysis n=%d     upload: %-16s %8.2f ms\n", n};  // diagnostics
     Arena ar;
     rsp_k::SolveTermsArgs tl{}, tt{};
     if (dev_terms) {
         dag_upload_rows(ar, f->L, hp->L, n, tl);
         dag_upload_rows(ar, f->LT, hp->LT, n, tt);
         tl.kind = 0;
-        tl.rp = d_row_offsets;
-        tl.ci = d_col_ind;
+        tl.rp = f->fac.rowptr;
+        tl.ci = f->fac.colidx;
         // the split term order (rsp_an::split_terms); none (nullptr) for the
         // reference's order
         if (!hp->lpos.empty()) {
-            ar.up((int **)&tl.lpos, hp->lpos);
-            ar.up((int **)&tl.ne, hp->ne_l);
-            ar.up((int **)&tt.ne, hp->ne_lt);
+            ar.up(&tl.lpos, hp->lpos);
+            ar.up(&tl.ne, hp->ne_l);
+            ar.up(&tt.ne, hp->ne_lt);
         }
         tt.kind = 1;
-        ar.up((int **)&tt.ltp, hp->ltp);
-        ar.up((int **)&tt.lts, hp->lts);
-        ar.up((int **)&tt.ltc, hp->ltc);
+        ar.up(&tt.ltp, hp->ltp);
+        ar.up(&tt.lts, hp->lts);
+        ar.up(&tt.ltc, hp->ltc);
     } else {
         dag_upload(ar, f->L, hp->L);
         dag_upload(ar, f->LT, hp->LT);
@@ -731,10 +668,10 @@ rsp_status_t rsp_api::ilu_solves_ready(rsp_handle_t h, rsp_ilu0_info *f) {
     ar.space(&f->d_sx, (size_t)std::max(n, 1) * sizeof(double));
     ar.space(&f->d_sdg, (size_t)std::max(n, 1) * sizeof(double));
     up_step("arena build");
-    hipError_t e = ar.commit(&f->d_arena_s, h->stream);
+    hipError_t e = ar.commit(f->arena_s, h->stream);
     up_step("commit (H2D)");
     if (e == hipSuccess && dev_terms) {
-        tl.dpos = f->d_dpos;
+        tl.dpos = f->fac.dpos;
         e = dag_build_terms(f->L, tl, h->stream);
         if (e == hipSuccess) e = dag_build_terms(f->LT, tt, h->stream);
     }
@@ -748,11 +685,7 @@ rsp_status_t rsp_api::ilu_solves_ready(rsp_handle_t h, rsp_ilu0_info *f) {
         f->digest = e == hipSuccess && f->digest ? rsp_an::digest(*hp) : 0;
     }
     if (e != hipSuccess) {
-        if (f->d_arena_s) (void)hipFree(f->d_arena_s);
-        f->d_arena_s = nullptr;
-        f->L = f->LT = rsp_ilu0_info::Dag();
-        f->Lb = f->LTb = rsp_ilu0_info::BlkDag();
-        f->analysed = 0;  // (the factor's L levels went with L: analyse again)
+        f->reset();  // (half-uploaded plans: analyse again)
         return e == hipErrorOutOfMemory ? RSP_STATUS_ALLOC_FAILED : RSP_STATUS_EXECUTION_FAILED;
     }
     // host copies kept for the U plan, built on first use (rsp_trsv_upper)
@@ -776,19 +709,18 @@ rsp_status_t rsp_api::ilu_solves_ready(rsp_handle_t h, rsp_ilu0_info *f) {
 
 // The U DAG's plan (rsp_trsv_upper, the --true-lu extension), on first use.
 rsp_status_t rsp_api::ilu_plan_u(rsp_handle_t h, rsp_ilu0_info *f) {
-    if (f->U.d_ptr) return RSP_STATUS_SUCCESS;
+    if (f->U.plan.ptr_dev) return RSP_STATUS_SUCCESS;
     if (!f->host) return RSP_STATUS_INTERNAL_ERROR;
     rsp_an::plan_u(f->host_rp.data(), f->host_ci.data(), *f->host);
     Arena ar;
     dag_upload(ar, f->U, f->host->U);
     // its streams (the L / L^T ones are sized for those DAGs' terms)
     ar.space(&f->d_usval, (size_t)std::max(f->U.nterms, 1) * sizeof(double));
-    hipError_t e = ar.commit(&f->d_arena_u, h->stream);
+    hipError_t e = ar.commit(f->arena_u, h->stream);
     f->host->U = rsp_an::DagHost();
-    if (e != hipSuccess) {
-        if (f->d_arena_u) (void)hipFree(f->d_arena_u);
-        f->d_arena_u = nullptr;
-        f->U = rsp_ilu0_info::Dag();
+    if (e != hipSuccess) {  // (L and L^T stay usable)
+        f->arena_u = DevMem();
+        f->U = Dag();
         return e == hipErrorOutOfMemory ? RSP_STATUS_ALLOC_FAILED : RSP_STATUS_EXECUTION_FAILED;
     }
     return RSP_STATUS_SUCCESS;
@@ -798,22 +730,12 @@ extern "C" {
 
 rsp_status_t rsp_create_ilu0_info(rsp_ilu0_info_t *info) {
     if (!info) return RSP_STATUS_INVALID_VALUE;
-    rsp_ilu0_info *f = new (std::nothrow) rsp_ilu0_info();
-    if (!f) return RSP_STATUS_ALLOC_FAILED;
-    f->analysed = 0;
-    f->structural_zero = -1;
-    f->factored = 0;
-    f->d_dpos = f->d_hasdiag = nullptr;
-    f->d_zero = nullptr;
-    f->d_upd_ptr = f->d_upd_l = f->d_upd_u = f->d_lord = f->d_lend = f->d_udiv = nullptr;
-    f->n_updates = 0;
-    *info = f;
-    return RSP_STATUS_SUCCESS;
+    *info = new (std::nothrow) rsp_ilu0_info();
+    return *info ? RSP_STATUS_SUCCESS : RSP_STATUS_ALLOC_FAILED;
 }
 
 rsp_status_t rsp_destroy_ilu0_info(rsp_ilu0_info_t info) {
     if (!info) return RSP_STATUS_INVALID_VALUE;
-    ilu_free_device(info);
     delete info;
     return RSP_STATUS_SUCCESS;
 }
@@ -831,10 +753,7 @@ rsp_status_t rsp_ilu0_analysis(rsp_handle_t h, int n, int nnz, const int *d_row_
                                const int *d_col_ind, rsp_ilu0_info_t f) {
     return guarded([&] { return ilu0_analysis(h, n, nnz, d_row_offsets, d_col_ind, f); },
                    [&] {
-                       if (f) {
-                           ilu_free_device(f);
-                           f->analysed = 0;
-                       }
+                       if (f) f->reset();
                    });
 }
 
@@ -880,8 +799,8 @@ rsp_status_t rsp_ilu0_solve_blocks(rsp_ilu0_info_t f, int *blocks_lower, int *bl
     return guarded([&] {
         if (!f || !blocks_lower || !blocks_upper || !f->analysed) return RSP_STATUS_INVALID_VALUE;
         RSP_TRY(ilu_solves_ready(f->han, f));
-        *blocks_lower = f->Lb.on ? f->Lb.nb : 0;
-        *blocks_upper = f->LTb.on ? f->LTb.nb : 0;
+        *blocks_lower = f->Lb.on ? f->Lb.args.nb : 0;
+        *blocks_upper = f->LTb.on ? f->LTb.args.nb : 0;
         return RSP_STATUS_SUCCESS;
     });
 }

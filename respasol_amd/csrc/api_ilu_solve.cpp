@@ -29,32 +29,22 @@ static rsp::FlowCtl flow_ctl(rsp_ilu0_info *f, int word, int gen) {
     return c;
 }
 
-static rsp::LevelPlan level_plan(const rsp_ilu0_info::Dag &d, const rsp_an::hvec<rsp::LevelSeg> &segs,
-                                 int batch) {
-    rsp::LevelPlan p;
-    p.rows = d.d_rows;
-    p.ptr_dev = d.d_ptr;
+// A DAG's plan for one call: its device arrays as uploaded (Dag::plan), the
+// host arrays' addresses as they are now (a Dag may have been assigned since).
+static rsp::LevelPlan level_plan(const rsp_ilu0_info::Dag &d, const rsp_an::hvec<rsp::LevelSeg> &segs, int batch) {
+    rsp::LevelPlan p = d.plan;
     p.ptr_host = d.ptr.data();
     p.nlev = (int)d.ptr.size() - 1;
     p.segs = segs.data();
     p.nseg = (int)segs.size();
     p.batch = batch;
     p.group = d.group;
-    p.tasks = d.d_tasks;
-    p.sbase_host = d.sbase.empty() ? nullptr : d.sbase.data();
-    p.tpos = d.d_tpos;
-    p.src = d.d_src;
-    p.chunks = d.d_chunks;
-    p.trow = d.d_trow;
-    p.sid = d.d_sid;
-    p.stg = d.d_stg;
-    p.fitems = d.d_fitems;
-    p.has_flow = 0;
-    for (const rsp::LevelSeg &sg : segs) p.has_flow |= !sg.thin && sg.c1 > sg.c0;
     p.nterms = d.nterms;
-    p.nshort = d.d_nshort;
     p.nshort_host = d.nshort.data();
     p.nwave_host = d.nwave.empty() ? nullptr : d.nwave.data();
+    p.sbase_host = d.sbase.empty() ? nullptr : d.sbase.data();
+    p.has_flow = 0;
+    for (const rsp::LevelSeg &sg : segs) p.has_flow |= !sg.thin && sg.c1 > sg.c0;
     return p;
 }
 
@@ -62,42 +52,19 @@ static bool flow_recover() { return env_int("RSP_ILU_FLOW_RECOVER", 1) != 0; }
 
 // One factor call (flow_ok = false: no flow launch, every fat level its own
 // launch — the recovery run of rsp_ilu0_zero_pivot).
-static rsp_status_t ilu_factor_run(rsp_handle_t h, rsp_ilu0_info_t f, rsp_datatype_t value_type,
-                                   void *d_values, bool flow_ok) {
+static rsp_status_t ilu_factor_run(rsp_handle_t h, rsp_ilu0_info *f, rsp_datatype_t value_type, void *d_values,
+                                   bool flow_ok) {
     RSP_CHECK_HIP(hipMemsetD32Async(f->d_zero, INT_MAX, 1, h->stream));
-    rsp::IluArgs a;
-    a.n = f->n;
-    a.rowptr = f->rowptr;
-    a.colidx = f->colidx;
-    a.dpos = f->d_dpos;
-    a.hasdiag = f->d_hasdiag;
+    rsp::IluArgs a = f->fac;  // the pattern, the symbolic arrays, the factor plan; this call's:
     a.vals = d_values;
-    a.zero_pivot = f->d_zero;
-    a.upd_ptr = f->d_upd_ptr;
-    a.upd_l = f->d_upd_l;
-    a.upd_u = f->d_upd_u;
-    a.lord = f->d_lord;
-    a.lend = f->d_lend;
-    a.udiv = f->d_udiv;
-    a.frow = f->d_frow;
-    a.fslots = f->d_fslots;
     a.fslev = f->fslev.empty() ? nullptr : f->fslev.data();
-    a.fat_slots = f->d_fslots && env_int("RSP_ILU_FAT_SLOT", 1) != 0;
+    a.fat_slots = a.fslots && env_int("RSP_ILU_FAT_SLOT", 1) != 0;
     a.fat_lds = env_int("RSP_ILU_FAT_LDS", 1) != 0;
     a.defer_rounds = env_int("RSP_ILU_DEFER", 8);  // A/B knob (thin factor runs)
     a.narrow_waves = std::min(std::max(env_int("RSP_ILU_FNARROW_WAVES", 4), 1), rsp::kThinThreads / 64);
-    a.rchunks = f->d_rchunks;
-    a.ritems = f->d_ritems;
-    a.rpairs = f->d_rpairs;
-    a.rstaged = f->d_rstaged;
-    a.rrounds = f->d_rrounds;
     a.plan = level_plan(f->fdag(), f->fac_segs, f->fac_batch);
-    a.fac_one = f->fac_scale;
-    a.fitems = f->d_ffitems;
     a.fruns = f->fruns.empty() ? nullptr : f->fruns.data();
     a.nfruns = a.fat_slots ? (int)f->fruns.size() : 0;
-    a.lev = nullptr;
-    a.forig = f->d_forig;
     if (f->fac_gen >= (1 << 30)) {  // generations wrap
         RSP_CHECK_HIP(hipMemsetD32Async(f->d_zero + 1, 0, 1, h->stream));  // no stale give-up
         f->fac_gen = 0;
@@ -113,8 +80,6 @@ static rsp_status_t ilu_factor_run(rsp_handle_t h, rsp_ilu0_info_t f, rsp_dataty
     const char *trace_file = getenv("RSP_ILU_FTRACE");
     unsigned long long *&d_trace = h->d_ftrace;
     const int trace_cap = 1 << 22;
-    a.trace = nullptr;
-    a.trace_cap = 0;
     if (trace_file) {
         if (!d_trace) RSP_CHECK_HIP(hipMalloc((void **)&d_trace, trace_cap * sizeof(unsigned long long)));
         RSP_CHECK_HIP(hipMemsetAsync(d_trace, 0, trace_cap * sizeof(unsigned long long), h->stream));
@@ -145,25 +110,24 @@ static rsp_status_t ilu_factor_run(rsp_handle_t h, rsp_ilu0_info_t f, rsp_dataty
 }
 
 // rsp_ilu0_factor: the input values kept for a recovery run, then the factor.
-static rsp_status_t ilu0_factor(rsp_handle_t h, rsp_ilu0_info_t f, rsp_datatype_t value_type, void *d_values) {
+static rsp_status_t ilu0_factor(rsp_handle_t h, rsp_ilu0_info *f, rsp_datatype_t value_type, void *d_values) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!f || !f->analysed || (f->nnz_s > 0 && !d_values)) return RSP_STATUS_INVALID_VALUE;
     if (value_type != RSP_R_64F && value_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
     // a factor with flow runs keeps its input values for a recovery run
-    // (rsp_ilu0_info::d_fbackup): one device copy of the values per call
+    // (rsp_ilu0_info::fbackup): one device copy of the values per call
     f->last_fac.valid = 0;
-    const bool flows = !f->fruns.empty() && f->d_fslots && env_int("RSP_ILU_FLOW", 1) != 0 &&
+    const bool flows = !f->fruns.empty() && f->fac.fslots && env_int("RSP_ILU_FLOW", 1) != 0 &&
                        env_int("RSP_ILU_FAT_SLOT", 1) != 0;
     if (flows && f->nnz_s > 0 && flow_recover()) {
         const size_t bytes = (size_t)f->nnz_s * elem_size(value_type);
         if (f->fbackup_bytes < bytes) {
-            if (f->d_fbackup) (void)hipFree(f->d_fbackup);
-            f->d_fbackup = nullptr;
+            f->fbackup = DevMem();
             f->fbackup_bytes = 0;
-            RSP_CHECK_HIP(hipMalloc(&f->d_fbackup, bytes));
+            RSP_CHECK_HIP(hipMalloc(&f->fbackup.p, bytes));
             f->fbackup_bytes = bytes;
         }
-        RSP_CHECK_HIP(hipMemcpyAsync(f->d_fbackup, d_values, bytes, hipMemcpyDeviceToDevice, h->stream));
+        RSP_CHECK_HIP(hipMemcpyAsync(f->fbackup.p, d_values, bytes, hipMemcpyDeviceToDevice, h->stream));
         f->last_fac.valid = 1;
         f->last_fac.seq = ++f->call_seq;
         f->last_fac.ftz = h->ftz;
@@ -177,10 +141,10 @@ static rsp::TrsvArgs trsv_args(rsp_handle_t h, rsp_ilu0_info *f, const void *alp
                                const void *vals, const void *x, void *y) {
     rsp::TrsvArgs a;
     a.n = f->n;
-    a.rowptr = f->rowptr;
-    a.colidx = f->colidx;
-    a.dpos = f->d_dpos;
-    a.hasdiag = f->d_hasdiag;
+    a.rowptr = f->fac.rowptr;
+    a.colidx = f->fac.colidx;
+    a.dpos = f->fac.dpos;
+    a.hasdiag = f->fac.hasdiag;
     a.vals = vals;
     a.x = x;
     a.y = y;
@@ -239,7 +203,7 @@ static void remember_solve(rsp_handle_t h, rsp_ilu0_info *f, int which, rsp_oper
 
 // flow_ok = false: the recovery run of rsp_trsv_zero_pivot (no flow launch)
 rsp_status_t rsp_api::rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t op, const void *alpha,
-                                               rsp_ilu0_info_t f, rsp_datatype_t value_type,
+                                               rsp_ilu0_info *f, rsp_datatype_t value_type,
                                                const void *d_values, const void *d_x, void *d_y, bool flow_ok) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!f || !f->analysed || !alpha) return RSP_STATUS_INVALID_VALUE;
@@ -268,35 +232,18 @@ rsp_status_t rsp_api::rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t o
     }
     hipError_t e;
     const bool f64 = value_type == RSP_R_64F, ftz = h->ftz != 0;
-    if (op != RSP_OPERATION_NON_TRANSPOSE && op != RSP_OPERATION_TRANSPOSE) return RSP_STATUS_INVALID_VALUE;
     RSP_CHECK_HIP(trsv_begin(h, f, op == RSP_OPERATION_NON_TRANSPOSE ? RSP_TRSV_L : RSP_TRSV_LT, a));
     // a deep DAG: the block-inverse solve (trsv_blocks.hip; RSP_ILU_BLOCKS=0
     // at solve time runs the level-scheduled solve of the same analysis)
     const rsp_ilu0_info::BlkDag &bd = op == RSP_OPERATION_NON_TRANSPOSE ? f->Lb : f->LTb;
     if (bd.on && env_int("RSP_ILU_BLOCKS", -1) != 0) {
-        rsp::BlkArgs b{};
-        b.n = f->n;
-        b.nb = bd.nb;
-        b.order = bd.d_order;
-        b.desc = bd.d_desc;
-        b.rows = bd.d_rows;
-        b.ref = bd.d_ref;
-        b.vpos = bd.d_vpos;
-        b.eord = bd.d_eord;
-        b.lptr = bd.d_lptr;
-        b.rptr = bd.d_rptr;
-        b.rit = bd.d_rit;
+        rsp::BlkArgs b = bd.args;  // the plan and its scratch; this call's:
         b.segs = bd.segs.data();
         b.nseg = (int)bd.segs.size();
-        b.lds_elems = bd.lds_elems;
-        b.lds_words = bd.lds_words;
-        b.rc = bd.d_rc;
         b.vals = d_values;
         b.x = d_x;
         b.y = d_y;
         b.alpha = a.alpha;
-        b.ev = bd.d_ev;
-        b.yp = bd.d_yp;
         e = f64 ? rsp_k::trsv_blocks_f64(b, h->stream)
                 : (ftz ? rsp_k_ftz::trsv_blocks_f32(b, h->stream) : rsp_k::trsv_blocks_f32(b, h->stream));
         return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
@@ -304,12 +251,10 @@ rsp_status_t rsp_api::rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t o
     if (op == RSP_OPERATION_NON_TRANSPOSE) {
         e = f64 ? rsp_k::trsv_lower_n_f64(a, h->stream)
                 : (ftz ? rsp_k_ftz::trsv_lower_n_f32(a, h->stream) : rsp_k::trsv_lower_n_f32(a, h->stream));
-    } else if (op == RSP_OPERATION_TRANSPOSE) {
+    } else {
         a.plan = level_plan(f->LT, f->LT.segs, f->LT.batch);
         e = f64 ? rsp_k::trsv_lower_t_f64(a, h->stream)
                 : (ftz ? rsp_k_ftz::trsv_lower_t_f32(a, h->stream) : rsp_k::trsv_lower_t_f32(a, h->stream));
-    } else {
-        return RSP_STATUS_INVALID_VALUE;
     }
     if (trace_file && e == hipSuccess) {
         rsp_an::hvec<unsigned long long> t(trace_cap);
@@ -332,7 +277,7 @@ rsp_status_t rsp_api::rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t o
     return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
 }
 
-rsp_status_t rsp_api::rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_ilu0_info_t f,
+rsp_status_t rsp_api::rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_ilu0_info *f,
                                           rsp_datatype_t value_type, const void *d_values, const void *d_x,
                                           void *d_y, bool flow_ok) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
@@ -357,7 +302,7 @@ rsp_status_t rsp_api::rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp
     return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
 }
 
-/* ------- recovery of a flow give-up (rsp_ilu0_info::d_fbackup / last_solve) */
+/* ------- recovery of a flow give-up (rsp_ilu0_info::fbackup / last_solve) */
 
 // Re-run one recorded solve without flow launches (rsp_ilu0_info::last_solve).
 static rsp_status_t rerun_solve(rsp_handle_t h, rsp_ilu0_info *f, int which) {
@@ -430,7 +375,7 @@ static rsp_status_t rerun_solves(rsp_handle_t h, rsp_ilu0_info *f, const LaterSo
 
 // rsp_ilu0_zero_pivot: the structural or numerical zero pivot of the last
 // factor, after the recovery of a factor whose flow wait gave up.
-static rsp_status_t ilu0_zero_pivot(rsp_handle_t h, rsp_ilu0_info_t f, int *position) {
+static rsp_status_t ilu0_zero_pivot(rsp_handle_t h, rsp_ilu0_info *f, int *position) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!f || !position) return RSP_STATUS_INVALID_VALUE;
     *position = -1;
@@ -440,14 +385,14 @@ static rsp_status_t ilu0_zero_pivot(rsp_handle_t h, rsp_ilu0_info_t f, int *posi
     RSP_CHECK_HIP(hipMemcpyAsync(z, f->d_zero, sizeof(z), hipMemcpyDeviceToHost, h->stream));
     RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
     // the last factor's flow wait gave up: its values are wrong. Recovered
-    // (rsp_ilu0_info::d_fbackup): the input values restored, the factor run
+    // (rsp_ilu0_info::fbackup): the input values restored, the factor run
     // again without flow launches; else reported.
     if (f->factored && f->fac_gen > 0 && z[1] == f->fac_gen) {
         if (!f->last_fac.valid || !flow_recover()) return RSP_STATUS_EXECUTION_FAILED;
         const LaterSolves later = later_solves(f, f->last_fac.seq);
         if (!rerun_inputs_intact(f, -1, later)) return RSP_STATUS_EXECUTION_FAILED;
         f->last_fac.valid = 0;
-        RSP_CHECK_HIP(hipMemcpyAsync(f->last_fac.vals, f->d_fbackup, (size_t)f->nnz_s * elem_size(f->last_fac.type),
+        RSP_CHECK_HIP(hipMemcpyAsync(f->last_fac.vals, f->fbackup.p, (size_t)f->nnz_s * elem_size(f->last_fac.type),
                                      hipMemcpyDeviceToDevice, h->stream));
         const int ftz = h->ftz;
         h->ftz = f->last_fac.ftz;  // the mode of the call being re-run
@@ -472,7 +417,7 @@ static rsp_status_t ilu0_zero_pivot(rsp_handle_t h, rsp_ilu0_info_t f, int *posi
 // solve of that kind gave up a flow wait (its y is wrong; never expected, a
 // bound instead of a GPU hang). The unit-lower solves have no pivots; the U
 // solve (extension) reports the factor's zero pivot, which it divides by.
-static rsp_status_t trsv_zero_pivot(rsp_handle_t h, rsp_ilu0_info_t f, int which, int *position) {
+static rsp_status_t trsv_zero_pivot(rsp_handle_t h, rsp_ilu0_info *f, int which, int *position) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!f || !position || which < RSP_TRSV_L || which > RSP_TRSV_U) return RSP_STATUS_INVALID_VALUE;
     *position = -1;

@@ -1,6 +1,7 @@
 // rsp_internal.h — what the host units of librsp.so share: the three structs
-// behind the opaque handles of include/rsp.h, the status macros, guarded()
-// and the few functions one unit calls in another (namespace rsp_api).
+// behind the opaque handles of include/rsp.h (the ILU(0) info is the state of
+// one analysis, reset whole by the next), the status macros, guarded() and the
+// few functions one unit calls in another (namespace rsp_api).
 //   rsp_api.cpp           handle, matrix descriptor, SpMV (plan upload, run, batch)
 //   spmv_plan.cpp         the SpMV planner (spmv_plan.h; no HIP calls)
 //   api_ilu_analysis.cpp  ILU(0) analysis, the solve plans, the plan queries
@@ -76,92 +77,90 @@ struct rsp_spmat {
     unsigned long long plan_gen;  // unique per plan / value rebind (batch staleness key)
 };
 
+// A hipMalloc'ed allocation, freed with its owner (move-only).
+struct DevMem {
+    void *p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem &operator=(DevMem &&o) noexcept {
+        std::swap(p, o.p);  // (the old allocation goes with o)
+        return *this;
+    }
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// Everything one rsp_ilu0_analysis produces and the calls on it change:
+// nothing in the info outlives an analysis, and reset() drops it.
+// Each plan array's device pointer lives in the kernel-argument struct it is
+// passed in (fac, Dag::plan, BlkDag::args), filled where the array is uploaded.
+// Member order is the destruction order's reverse: the planning task is
+// declared after host / host_rp / host_ci, which it reads, so it is destroyed
+// (joined) before them; nothing depends on the order of the rest.
 struct rsp_ilu0_info {
-    int analysed;
-    int n, nnz_s;
-    const int *rowptr, *colidx;  // device pattern captured at analysis
-    int structural_zero;         // -1 = none
-    int factored;
-    int *d_dpos, *d_hasdiag;
-    int *d_upd_ptr, *d_upd_l, *d_upd_u, *d_lord, *d_lend, *d_udiv;
+    int analysed = 0, factored = 0;
+    int n = 0, nnz_s = 0;
+    int structural_zero = -1;  // -1 = none
+    rsp_handle_t han = nullptr;  // the handle of the analysis (its stream uploads the solve plans)
+    long long n_updates = 0;
+    // The factor's arguments but for those of one call (ilu_factor_run): the
+    // pattern captured at analysis, the symbolic arrays, the factor plan.
+    rsp::IluArgs fac{};
     // d_zero: [0] numerical zero pivot (atomicMin), [1] generation of the
     // last factor call whose flow wait gave up, [2..4] the same for the L,
     // L^T and U solves (rsp::FlowCtl), [6..7] the flow claim counter
-    int *d_zero;
+    int *d_zero = nullptr;
     unsigned long long claim_host = 0;  // flow claims issued (rsp::FlowCtl)
     int *d_fdone = nullptr;             // ticket flow launches: per item, the epoch that finished it (rsp::FlowCtl)
     unsigned *d_tk = nullptr;           // ticket flow launches: two slots of counters (rsp::FlowCtl::tickets)
     unsigned long long tk_seq = 0;      // ticket flow launches enqueued (rsp::FlowCtl::tk_seq)
     unsigned flow_epoch = 0;            // epochs handed out (rsp::FlowCtl)
+    int fac_gen = 0;
     int solve_gen[3] = {0, 0, 0};       // per solve kind: generation of the last call
-    long long n_updates;
     // one level set per DAG: L (factor + L solve), L^T, U
     struct Dag {
+        rsp::LevelPlan plan{};                  // the device arrays (the host fields: level_plan, per call)
         rsp_an::hvec<int> ptr;                  // host level pointers
-        int *d_rows = nullptr, *d_ptr = nullptr;
-        rsp::RowTask *d_tasks = nullptr;       // solve: task per level-order slot
-        int *d_tpos = nullptr, *d_src = nullptr;  // solve: flat terms
-        rsp::LevelChunk *d_chunks = nullptr;   // solve: LDS-staged chunks of thin runs
-        rsp::ThinRowPlan *d_trow = nullptr;    // solve: thin-run row records
-        int *d_sid = nullptr;                  // solve: thin-run y indices per term
-        rsp::StagedTerm *d_stg = nullptr;      // solve: thin-run staged terms
-        rsp::FlowItem *d_fitems = nullptr;     // solve: flow segments' work items
-        int nterms = 0;                        // solve: flat terms
-        int *d_nshort = nullptr;               // solve: short rows per level (device)
-        rsp_an::hvec<int> nshort;               // (host)
-        rsp_an::hvec<int> nwave;                // solve: short + wave rows per level (host)
-        rsp_an::hvec<int> sbase;                // solve: padded short rows' first term per level (host)
+        int nterms = 0;                         // solve: flat terms
+        rsp_an::hvec<int> nshort;               // solve: short rows per level
+        rsp_an::hvec<int> nwave;                // solve: short + wave rows per level
+        rsp_an::hvec<int> sbase;                // solve: padded short rows' first term per level
         rsp_an::hvec<rsp::LevelSeg> segs;       // thread-per-row solve plan
-        int batch = 8;                         // solve fma-chain batch
-        int group = 4;                         // thin-run term groups (2 or 4)
-    } L, LT, U, F;  // F: the factor's one level when fac_one (ptr, d_rows, d_ptr; rsp_an::IluHostPlan::F)
+        int batch = 8;                          // solve fma-chain batch
+        int group = 4;                          // thin-run term groups (2 or 4)
+    } L, LT, U, F;  // F: the factor's one level when fac_one (ptr, rows, ptr_dev; rsp_an::IluHostPlan::F)
     // block-inverse solve plans of deep L / L^T DAGs (rsp_an::plan_blocks,
     // trsv_blocks.hip); on = false: the level-scheduled solve runs
     struct BlkDag {
         bool on = false;
-        int nb = 0, lds_elems = 0, lds_words = 0, entries = 0, nlong = 0;
+        rsp::BlkArgs args{};             // the plan and its scratch (the call's fields: the solve)
         rsp_an::hvec<rsp::BlkSeg> segs;  // host
-        int *d_order = nullptr, *d_ref = nullptr, *d_vpos = nullptr, *d_lptr = nullptr, *d_rptr = nullptr;
-        rsp::BlkDesc *d_desc = nullptr;
-        rsp::BlkRow *d_rows = nullptr;
-        unsigned *d_eord = nullptr, *d_rit = nullptr;
-        void *d_ev = nullptr, *d_yp = nullptr;  // scratch, fp64-sized
-        void *d_rc = nullptr;  // block records (fp64-sized: 64 x 144 B per block)
     } Lb, LTb;
-    bool fac_one = false, fac_scale = false;  // fac_scale: the factor is ilu0_scale_lower (IluHostPlan::fac_scale)
+    bool fac_one = false;  // the factor walks F (fac.fac_one: it is ilu0_scale_lower, IluHostPlan::fac_scale)
     const Dag &fdag() const { return fac_one ? F : L; }  // the factor's level sets
     rsp_an::hvec<rsp::LevelSeg> fac_segs;       // wave-per-row factor plan over fdag()
-    void *d_sval = nullptr, *d_sx = nullptr, *d_sdg = nullptr;  // solve streams (trsv_stream)
-    rsp::RndChunk *d_rchunks = nullptr;        // round-based factor chunks (thin runs)
-    rsp::RndItem *d_ritems = nullptr;
-    rsp::FacRow *d_frow = nullptr;
-    int *d_fslots = nullptr;                   // fat factor levels, slot layout (ilu0_level_slot)
+    int fac_batch = 8;
     rsp_an::hvec<rsp::FacFlowRun> fruns;        // factor flow runs (ilu0_flow)
-    rsp::FacFlowItem *d_ffitems = nullptr;
-    void *d_forig = nullptr;                   // flow rows' upper input values (ilu0_flow_prep), fp64-sized
-    int fac_gen = 0;
     rsp_an::hvec<rsp::FacSlotLevel> fslev;      // per factor level (stride 0: FacRow path)
-    int *d_rpairs = nullptr, *d_rstaged = nullptr, *d_rrounds = nullptr;
-    int fac_batch;
-    void *d_arena = nullptr;    // one allocation holding the analysis' arrays (Arena)
-    void *d_arena_u = nullptr;  // the U plan's (built on first use)
-    void *d_arena_sym = nullptr;    // device analysis: dpos, hasdiag, upd_ptr, lord, lend, udiv, scratch
-    void *d_arena_pairs = nullptr;  // device analysis: upd_l, upd_u
-    void *d_usval = nullptr;    // U solve term values (trsv_stream), in d_arena_u
-    unsigned long long digest = 0;  // rsp_an::digest of the host plan
+    void *d_sval = nullptr, *d_sx = nullptr, *d_sdg = nullptr;  // solve streams (trsv_stream)
+    void *d_usval = nullptr;    // U solve term values (trsv_stream), in arena_u
+    DevMem arena;        // one allocation holding the analysis' arrays (Arena)
+    DevMem arena_sym;    // device analysis: dpos, hasdiag, upd_ptr, lord, lend, udiv, scratch
+    DevMem arena_pairs;  // device analysis: upd_l, upd_u
+    DevMem arena_s;      // the solve plans'
+    DevMem arena_u;      // the U plan's (built on first use)
+    DevMem fslots;       // fat factor levels, slot layout (ilu0_level_slot; fac.fslots once built)
+    unsigned long long digest = 0;  // rsp_an::digest of the host plan (RSP_ILU_DIGEST; 0: none)
     std::unique_ptr<rsp_an::IluHostPlan> host;  // kept for the solve plans and the U plan
     rsp_an::hvec<int> host_rp, host_ci;
     // The L and L^T solve plans (the reference's two csrsv2_analysis calls,
     // GPU/ilu0.cu:228-252): built on a worker thread that rsp_ilu0_analysis
     // starts once the levels exist and leaves running; ilu_solves_ready
     // (rsp_trsv_analysis, or the first solve) joins it and uploads them.
-    // (Declared after host / host_rp / host_ci, which it reads: destroyed,
-    // i.e. joined, before them.)
     std::unique_ptr<rsp_an::Task> solves_task;
     bool solves_ready = false;
     bool dev_terms = true;      // the per-term half of the solve plans is built on the device
-    void *d_arena_s = nullptr;  // the solve plans' allocation
-    rsp_handle_t han = nullptr; // the handle of the analysis (its stream uploads the solve plans)
     // Recovery of a call whose flow wait gave up (a co-running kernel kept
     // some of the flow launch's workgroups from being scheduled past the
     // give-up bound): rsp_ilu0_zero_pivot / rsp_trsv_zero_pivot re-run it
@@ -172,7 +171,7 @@ struct rsp_ilu0_info {
     // A recovered call's output feeds the calls made after it (the L^T solve
     // reads the L solve's y; a solve reads the factor's values), so those are
     // re-run too, in call order (seq).
-    void *d_fbackup = nullptr;
+    DevMem fbackup;
     size_t fbackup_bytes = 0;
     long long call_seq = 0;
     struct FacCall {
@@ -192,6 +191,13 @@ struct rsp_ilu0_info {
         const void *vals = nullptr, *x = nullptr;
         void *y = nullptr;
     } last_solve[3];
+
+    // Drop the analysis: as rsp_create_ilu0_info made it. (Never by a bare
+    // assignment: memberwise, that frees the buffers before joining the task.)
+    void reset() {
+        solves_task.reset();
+        *this = rsp_ilu0_info();
+    }
 };
 
 #define RSP_CHECK_HIP(call)                                                     \
@@ -252,10 +258,10 @@ rsp_status_t ilu_plan_u(rsp_handle_t h, rsp_ilu0_info *f);
 // api_ilu_solve.cpp
 // The solves behind rsp_trsv_lower_unit / rsp_trsv_upper (flow_ok = false: the
 // recovery run, no flow launch).
-rsp_status_t rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t op, const void *alpha, rsp_ilu0_info_t f,
+rsp_status_t rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t op, const void *alpha, rsp_ilu0_info *f,
                                       rsp_datatype_t value_type, const void *d_values, const void *d_x, void *d_y,
                                       bool flow_ok);
-rsp_status_t rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_ilu0_info_t f, rsp_datatype_t value_type,
+rsp_status_t rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_ilu0_info *f, rsp_datatype_t value_type,
                                  const void *d_values, const void *d_x, void *d_y, bool flow_ok);
 
 }  // namespace rsp_api

@@ -363,6 +363,140 @@ def test_trsv_analysis_lifecycle(handle):
     e.trsv_analysis(transpose=True)
 
 
+def _small(rp, ci, va):
+    n = len(rp) - 1
+    return csr.CsrMatrix(0, n, n, len(ci), np.array(rp, np.int32), np.array(ci, np.int32), np.array(va, np.float64))
+
+
+def _analyse_raw(handle, il, A):
+    """rsp_ilu0_analysis of the existing info il on fresh device arrays of A
+    (returned: the info keeps their addresses). -> status, rp, ci, va"""
+    from respasol_amd._lib import rsp
+    from respasol_amd.sparse import _ptr
+    if A.n > 0:
+        rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
+    else:
+        rp = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ci = torch.zeros(1, dtype=torch.int32, device="cuda")
+        va = torch.zeros(1, dtype=torch.float64, device="cuda")
+    st = rsp.rsp_ilu0_analysis(handle.ptr, A.n, A.nnz, _ptr(rp), _ptr(ci), il._info)
+    return st, rp, ci, va
+
+
+def test_one_info_through_a_sequence_of_patterns(handle, monkeypatch):
+    """One rsp_ilu0_info analysed with eight patterns in turn. Every analysis
+    replaces all the state of the one before: between them the patterns have
+    and lack block-inverse solve plans, factor flow runs, the slot layout,
+    the factor's own one-level DAG, host-built hub rows and a U plan (built on
+    first use after steps 1, 4 and 8); one is rejected, one is empty. After
+    each: factor, L, L^T (and U) bitwise the oracle's in fp64, levels and
+    block counts those of a fresh info."""
+    import ctypes as C
+    from respasol_amd import _lib
+    from respasol_amd._lib import rsp
+    monkeypatch.delenv("RSP_ILU_BLOCKS", raising=False)  # the default plans: blocks on deep DAGs
+    zero = _small([0], [], [])
+    steps = [("dc1", csr.surrogate("dc1", 0.3), True, True),
+             ("crashbasis", csr.surrogate("crashbasis", 0.1), False, False),
+             ("G2_circuit", csr.surrogate("G2_circuit", 0.05), False, True),
+             ("ss1", csr.surrogate("ss1", 0.05), True, False),
+             ("rejected", _small([0, 2, 4], [1, 0, 0, 1], [1.0] * 4), False, False),
+             ("chain", _small([0, 1, 3], [0, 0, 1], [2.0, -1.0, 3.0]), False, None),
+             ("empty", zero, False, None),
+             ("dc1", None, True, True)]
+    assert [s[1].n for s in steps[:4]] == [35051, 16000, 7505, 10264]
+    ref = {}  # per pattern, computed once: the oracle's results and a fresh info's plan figures
+
+    def reference(name, A):
+        if name in ref:
+            return ref[name]
+        x = csr.dlarnv(2, [0, 0, 0, 1], A.n)[0] if A.n else np.zeros(0)
+        fresh = Ilu0(handle, torch.zeros(1, dtype=torch.int32, device="cuda"), None, nnz=0)
+        st, *keep = _analyse_raw(handle, fresh, A)
+        assert st == 0
+        levels, blocks = fresh.levels(), fresh.solve_blocks()
+        fresh.close()
+        rv, sz, zp = ob.ilu0(A.rowptr, A.colidx, A.values)
+        assert sz == -1 and zp == -1
+        rz = ob.trsv("lower_n", A.rowptr, A.colidx, rv, x)  # (the block order where the product plans blocks)
+        ry = ob.trsv("lower_t", A.rowptr, A.colidx, rv, rz)
+        ru = ob.trsv("upper", A.rowptr, A.colidx, rv, rz)
+        ref[name] = (A, x, levels, blocks, rv, rz, ry, ru)
+        return ref[name]
+
+    il = Ilu0(handle, torch.zeros(1, dtype=torch.int32, device="cuda"), None, nnz=0)
+    for name, A, with_u, has_blocks in steps:
+        if name == "rejected":
+            st, *keep = _analyse_raw(handle, il, A)
+            assert st == _lib.STATUS_INVALID_VALUE
+            pos, lo, up = C.c_int(), C.c_int(), C.c_int()
+            assert rsp.rsp_ilu0_factor(handle.ptr, il._info, _lib.R_64F, keep[2].data_ptr()) == _lib.STATUS_INVALID_VALUE
+            assert rsp.rsp_trsv_analysis(handle.ptr, _lib.OP_N, il._info) == _lib.STATUS_INVALID_VALUE
+            assert rsp.rsp_ilu0_levels(il._info, C.byref(lo), C.byref(up)) == _lib.STATUS_INVALID_VALUE
+            assert rsp.rsp_ilu0_zero_pivot(handle.ptr, il._info, C.byref(pos)) == _lib.STATUS_INVALID_VALUE
+            assert rsp.rsp_trsv_zero_pivot(handle.ptr, il._info, il.TRSV_L, C.byref(pos)) == _lib.STATUS_INVALID_VALUE
+            continue
+        A, x, levels, blocks, rv, rz, ry, ru = reference(name, A if A is not None else ref[name][0])
+        st, *keep = _analyse_raw(handle, il, A)
+        assert st == 0, name
+        va = keep[2]
+        assert il.zero_pivot() == -1
+        il.factor(va)
+        xx = torch.from_numpy(x).cuda() if A.n else torch.zeros(1, dtype=torch.float64, device="cuda")
+        z = il.solve_lower(va, xx)
+        y = il.solve_lower(va, z, transpose=True)
+        u = il.solve_upper(va, z) if with_u else None
+        torch.cuda.synchronize()
+        assert il.zero_pivot() == -1
+        assert il.solve_zero_pivot(il.TRSV_L) == -1 and il.solve_zero_pivot(il.TRSV_LT) == -1
+        nn, nv = A.n, A.nnz
+        assert np.array_equal(va.cpu().numpy()[:nv], rv), name
+        assert np.array_equal(z.cpu().numpy()[:nn], rz), name
+        assert np.array_equal(y.cpu().numpy()[:nn], ry), name
+        if with_u:
+            assert il.solve_zero_pivot(il.TRSV_U) == -1
+            assert np.array_equal(u.cpu().numpy()[:nn], ru), name
+        assert il.levels() == levels, name
+        assert il.solve_blocks() == blocks, name
+        # (what keeps the test from passing vacuously: plans that come and go)
+        if has_blocks is not None:
+            assert (blocks[0] > 0 and blocks[1] > 0) if has_blocks else blocks == (0, 0), (name, blocks)
+    il.close()
+
+
+def test_digest_does_not_outlive_its_analysis(handle, monkeypatch):
+    """The plan digest (RSP_ILU_DIGEST, tests only) belongs to one analysis: a
+    re-analysis without the variable computes none, so rsp_ilu0_plan_digest is
+    INVALID_VALUE, not the previous pattern's digest; with it again and
+    another pattern, that pattern's."""
+    import ctypes as C
+    from respasol_amd import _lib
+    from respasol_amd._lib import rsp
+
+    def host_digest(A):
+        d = C.c_uint64()
+        r = np.ascontiguousarray(A.rowptr, np.int32)
+        c = np.ascontiguousarray(A.colidx, np.int32)
+        assert rsp.rsp_ilu0_analysis_host(A.n, r.ctypes.data, c.ctypes.data, None, None, C.byref(d), None) == 0
+        return d.value
+
+    A, B = csr.surrogate("dc1", 0.1), csr.surrogate("crashbasis", 0.1)
+    il = Ilu0(handle, torch.zeros(1, dtype=torch.int32, device="cuda"), None, nnz=0)
+    dev = C.c_uint64()
+    monkeypatch.setenv("RSP_ILU_DIGEST", "1")
+    st, *keep_a = _analyse_raw(handle, il, A)
+    assert st == 0 and rsp.rsp_ilu0_plan_digest(il._info, C.byref(dev)) == 0
+    assert dev.value == host_digest(A)
+    monkeypatch.delenv("RSP_ILU_DIGEST")
+    st, *keep_a2 = _analyse_raw(handle, il, A)
+    assert st == 0 and rsp.rsp_ilu0_plan_digest(il._info, C.byref(dev)) == _lib.STATUS_INVALID_VALUE
+    monkeypatch.setenv("RSP_ILU_DIGEST", "1")
+    st, *keep_b = _analyse_raw(handle, il, B)
+    assert st == 0 and rsp.rsp_ilu0_plan_digest(il._info, C.byref(dev)) == 0
+    assert dev.value == host_digest(B)
+    il.close()
+
+
 @pytest.mark.parametrize("thin_solve", [1024, 0])
 def test_fp32_fma_single_rounding(handle, monkeypatch, thin_solve):
     """fp32 solves fuse in fp32 (one rounding, fmaf), not in double: for
