@@ -101,6 +101,7 @@ rsp_status_t rsp_create_csr(rsp_spmat_t *mat, int64_t rows, int64_t cols, int64_
 /* Re-point the values array (e.g. fp64 -> fp32 copy) keeping the analysis:
  * the schedule stays for the same value_type; another type re-plans on the next
  * bufferSize / preprocess / SpMV (a tile's capacity depends on the type).
+ * The transposed side (rsp_spmv, op == TRANSPOSE), if built, follows suit.
  * INVALID_VALUE: a NULL mat, a value_type outside the enum. */
 rsp_status_t rsp_csr_set_values(rsp_spmat_t mat, void *d_values, rsp_datatype_t value_type);
 rsp_status_t rsp_destroy_spmat(rsp_spmat_t mat); /* cusparseDestroySpMat (GPU/spmv.cu:279) */
@@ -129,9 +130,9 @@ rsp_status_t rsp_spmv_buffer_size(rsp_handle_t handle, rsp_operation_t op, const
 rsp_status_t rsp_spmv_preprocess(rsp_handle_t handle, rsp_operation_t op, const void *alpha,
                                  rsp_spmat_t mat, const void *d_x, const void *beta, void *d_y,
                                  rsp_datatype_t compute_type, void *d_buffer);
-/* cusparseSpMV (GPU/spmv.cu:179-186): y = alpha * A * x + beta * y.
- * op must be NON_TRANSPOSE (the only form the reference uses). The rounding
- * is fixed: with T the compute type and s the row's products summed in the
+/* cusparseSpMV (GPU/spmv.cu:179-186): y = alpha * op(A) * x + beta * y, op
+ * NON_TRANSPOSE (the only form the reference uses) or TRANSPOSE (below). The
+ * rounding is fixed: with T the compute type and s the row's products summed in the
  * canonical order (spmv.hip; oracle_spmv_canon_* of oracle/rsp_oracle.h),
  *     y = round(round(alpha * s) + round(beta * y)),
  * each round() to T: two rounded products and one rounded sum, never a fused
@@ -145,7 +146,34 @@ rsp_status_t rsp_spmv_preprocess(rsp_handle_t handle, rsp_operation_t op, const 
  * otherwise, e.g. a type left over from before rsp_csr_set_values). Deterministic:
  * the same inputs give bitwise identical y on every call. `d_buffer` is
  * accepted for signature parity and unused. Calls on one matrix must be
- * stream-ordered (its long-row tickets live in its schedule). */
+ * stream-ordered (its long-row tickets live in its schedule).
+ *
+ * op == TRANSPOSE: y = alpha * A^T * x + beta * y, x of `rows` elements, y of
+ * `cols` (d_x is required when rows > 0, d_y when cols > 0; INVALID_VALUE
+ * otherwise). A^T is DEFINED as a CSR matrix: its row j holds the entries of
+ * column j of A in storage order — ascending row of A, and within a row the
+ * order they are stored in (a stable counting sort by column; duplicates and
+ * unsorted rows of A are legal and keep that order) — and s is the canonical
+ * order applied to that matrix. So the result is bit for bit that of op ==
+ * NON_TRANSPOSE on a descriptor over the rsp_csr2csc output, of
+ * oracle_spmv_canon_* on that transpose, and of itself on every repeat; no
+ * atomics, nothing depends on arrival order. The epilogue rule is the one
+ * above. Cost: the first bufferSize / preprocess / SpMV with op == TRANSPOSE
+ * builds (host-blocking, as bufferSize) a transposed side owned by `mat`:
+ * device memory of nnz * (8 + element size) + 4 * (cols + 1) bytes plus the
+ * schedule of A^T, freed by rsp_destroy_spmat; and every call runs a
+ * permutation pass over the values (they are read on every call, as for op ==
+ * NON_TRANSPOSE) before the product, both on the handle's stream. A caller
+ * whose values are static transposes once with rsp_csr2csc, creates a
+ * descriptor on the result and pays neither. bufferSize(op = TRANSPOSE) builds
+ * the side if absent (*buffer_size = 0), preprocess(op = TRANSPOSE) always
+ * rebuilds it from the pattern as it is then; neither touches the forward
+ * schedule. After rsp_csr_set_values the next call permutes the new values
+ * (another type: the permuted values are reallocated and A^T re-planned by
+ * that call; pattern arrays and permutation stay). rsp_spmat_set_local_cols
+ * concerns the forward schedule only; rsp_spmv_part and the batch calls are
+ * NON_TRANSPOSE only. A matrix never used with op == TRANSPOSE allocates
+ * nothing for it. An op outside the enum: NOT_SUPPORTED (all three calls). */
 rsp_status_t rsp_spmv(rsp_handle_t handle, rsp_operation_t op, const void *alpha, rsp_spmat_t mat,
                       const void *d_x, const void *beta, void *d_y, rsp_datatype_t compute_type,
                       void *d_buffer);
@@ -395,6 +423,23 @@ rsp_status_t rsp_gather(rsp_handle_t handle, rsp_datatype_t value_type, int64_t 
 rsp_status_t rsp_scatter(rsp_handle_t handle, rsp_datatype_t value_type, int64_t n,
                          const int64_t *d_idx, const void *d_src, void *d_dst);
 
+/* cusparseCsr2cscEx2 (CUSPARSE_ACTION_NUMERIC, index base 0): the CSC form
+ * of a rows x cols CSR matrix, i.e. the CSR form of A^T: d_csc_col_offsets
+ * (cols + 1), d_csc_row_ind and d_csc_values (offsets[rows] entries each), in
+ * the order rsp_spmv(op = TRANSPOSE) defines and uses (the same code). `nnz`
+ * is the caller's count, as in rsp_create_csr; offsets[rows] entries are
+ * transposed. Host-blocking: the pattern is read once and transposed on the
+ * host, the values are moved on the device as bits (a NaN payload or a
+ * denormal survives in every handle mode). d_values == NULL and
+ * d_csc_values == NULL: symbolic only. INVALID_VALUE: a malformed pattern (an
+ * offset that is negative or decreases, offsets[0] != 0, offsets[rows] > nnz,
+ * a column outside [0, cols)), a size outside int32, a NULL pointer that is
+ * needed (one of the two value arrays alone, too); nothing is written then. */
+rsp_status_t rsp_csr2csc(rsp_handle_t handle, int64_t rows, int64_t cols, int64_t nnz,
+                         const int *d_row_offsets, const int *d_col_ind, const void *d_values,
+                         rsp_datatype_t value_type, int *d_csc_col_offsets, int *d_csc_row_ind,
+                         void *d_csc_values);
+
 /* Schedule facts of the current schedule of `mat` (no cuSPARSE
  * counterpart; for byte accounting): its tile count, and how many stored
  * entries it reads through 16-bit column offsets (2 B each instead of the
@@ -486,6 +531,21 @@ rsp_status_t rsp_ilu0_analysis_host(int n, const int *row_offsets, const int *co
 rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
                                 rsp_datatype_t compute_type, int64_t *tiles, int64_t *entries_16bit,
                                 int64_t *entries_staged);
+/* Profiling (no cuSPARSE counterpart; scripts/bench_spmv_t.py): the
+ * permutation pass of rsp_spmv(op = TRANSPOSE) alone, on the handle's stream:
+ * the current values of `mat` into its transposed side, no product.
+ * NOT_INITIALIZED before the transposed side exists (or while it is of another
+ * type than the matrix, after rsp_csr_set_values). */
+rsp_status_t rsp_spmv_transpose_permute(rsp_handle_t handle, rsp_spmat_t mat);
+/* Tests (no device needed): the transposer behind rsp_spmv(op = TRANSPOSE)
+ * and rsp_csr2csc on HOST arrays (base 0): t_row_offsets (cols + 1),
+ * t_col_ind and perm (row_offsets[rows] entries each; entry k of A^T is entry
+ * perm[k] of A), a serial stable counting sort by column. Only
+ * row_offsets[rows] entries of col_ind are read. INVALID_VALUE for a
+ * malformed pattern (as rsp_csr2csc) or a NULL array that is needed; nothing
+ * is written then. */
+rsp_status_t rsp_csr_transpose_host(int64_t rows, int64_t cols, const int *row_offsets, const int *col_ind,
+                                    int *t_row_offsets, int *t_col_ind, int *perm);
 /* Tests and records (no device needed): what ONE call over the schedule of the
  * same host pattern reads besides the values, x and y, counted per tile on the
  * vector path. RSP_SPMV_PACK (0, 1, 2 = default; read when a schedule is built) selects

@@ -148,11 +148,107 @@ rsp_status_t rsp_api::spmv_plan(rsp_handle_t h, rsp_spmat_t mat, rsp_datatype_t 
     return RSP_STATUS_SUCCESS;
 }
 
+/* ------------------------------------------------- the transposed side */
+
+// The pattern of `mat` downloaded, validated and transposed on the host
+// (csr_transpose.h): what rsp_spmv(op = TRANSPOSE) and rsp_csr2csc share.
+struct HostTranspose {
+    rsp_an::hvec<int> rowptr, colidx, perm;
+    int64_t nnz = 0;  // rowptr[rows] of mat
+};
+
+static rsp_status_t transpose_pattern(rsp_handle_t h, rsp_spmat_t mat, HostTranspose &t) {
+    rsp_an::hvec<int> rp, ci;
+    RSP_TRY(download_pattern(h, mat, rp, ci));
+    t.nnz = mat->rows > 0 ? rp[(size_t)mat->rows] : 0;
+    if (mat->cols > INT_MAX - 1) return RSP_STATUS_INVALID_VALUE;  // A^T's rows
+    t.rowptr.assign((size_t)mat->cols + 1, 0);
+    t.colidx.assign((size_t)t.nnz, 0);
+    t.perm.assign((size_t)t.nnz, 0);
+    return rsp_tr::csr_transpose(mat->rows, mat->cols, rp.data(), ci.data(), t.rowptr.data(), t.colidx.data(),
+                                 t.perm.data());
+}
+
+static hipError_t upload_ints(rsp_handle_t h, void *dst, const rsp_an::hvec<int> &src) {
+    return src.empty() ? hipSuccess
+                       : hipMemcpyAsync(dst, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+}
+
+// (Re)build the transposed side of `mat` from its pattern as it is now
+// (host-blocking): pattern, permutation, room for the values and the child's
+// schedule. The old side, if any, is dropped only once the new one stands.
+static rsp_status_t tside_build(rsp_handle_t h, rsp_spmat_t mat) {
+    HostTranspose ht;
+    RSP_TRY(transpose_pattern(h, mat, ht));
+    std::unique_ptr<rsp_spmat_tside> t(new rsp_spmat_tside());
+    RSP_CHECK_HIP(hipGetDevice(&t->device));
+    const size_t off_ci = align256(ht.rowptr.size() * sizeof(int));
+    const size_t off_perm = off_ci + align256(ht.colidx.size() * sizeof(int));
+    const size_t bytes = off_perm + std::max<size_t>(align256(ht.perm.size() * sizeof(int)), 256);
+    RSP_CHECK_HIP(hipMalloc(&t->pattern.p, bytes));
+    RSP_CHECK_HIP(hipMalloc(&t->vt.p, std::max<size_t>((size_t)ht.nnz * elem_size(mat->type), 256)));
+    char *buf = (char *)t->pattern.p;
+    RSP_CHECK_HIP(upload_ints(h, buf, ht.rowptr));
+    RSP_CHECK_HIP(upload_ints(h, buf + off_ci, ht.colidx));
+    RSP_CHECK_HIP(upload_ints(h, buf + off_perm, ht.perm));
+    RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+    t->perm = (int *)(buf + off_perm);
+    rsp_spmat &c = t->child;  // (value-initialised: no schedule yet)
+    c.rows = mat->cols;
+    c.cols = mat->rows;
+    c.nnz = ht.nnz;
+    c.rowptr = (int *)buf;
+    c.colidx = (int *)(buf + off_ci);
+    c.vals = t->vt.p;
+    c.type = mat->type;
+    c.local_cols = -1;
+    RSP_TRY(rsp_api::spmv_plan(h, &c, c.type));
+    rsp_k::warm_transpose();  // (the permutation's code object, outside the timed calls)
+    delete mat->tside;
+    mat->tside = t.release();
+    return RSP_STATUS_SUCCESS;
+}
+
+// The transposed side of `mat`, built if absent, its values' room and the
+// child's type brought up to the matrix's (rsp_csr_set_values to the other
+// type: the pattern arrays and the permutation stay, the child re-plans).
+static rsp_status_t tside_ready(rsp_handle_t h, rsp_spmat_t mat) {
+    if (!mat->tside) return tside_build(h, mat);
+    rsp_spmat_tside *t = mat->tside;
+    if (t->child.type != mat->type) {
+        DevMem v;
+        RSP_CHECK_HIP(hipMalloc(&v.p, std::max<size_t>((size_t)t->child.nnz * elem_size(mat->type), 256)));
+        t->vt = std::move(v);  // (the old values go with v)
+        t->child.vals = t->vt.p;
+        t->child.type = mat->type;
+        t->child.planned = 0;
+    }
+    return RSP_STATUS_SUCCESS;
+}
+
+// y = alpha * A^T * x + beta * y: the permutation of the values as they are
+// now, then the ordinary product of the child, both on the handle's stream.
+static rsp_status_t spmv_run_transposed(rsp_handle_t h, const void *alpha, rsp_spmat_t mat, const void *d_x,
+                                        const void *beta, void *d_y, rsp_datatype_t compute_type, void *d_buffer) {
+    if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
+    if ((mat->rows > 0 && !d_x) || (mat->cols > 0 && !d_y)) return RSP_STATUS_INVALID_VALUE;
+    RSP_TRY(tside_ready(h, mat));
+    rsp_spmat_tside *t = mat->tside;
+    if (t->child.nnz > 0 && !mat->vals) return RSP_STATUS_INVALID_VALUE;
+    if (rsp_k::permute_values((int)elem_size(compute_type), t->child.nnz, t->perm, mat->vals, t->vt.p, h->num_cus,
+                              h->stream) != hipSuccess)
+        return RSP_STATUS_EXECUTION_FAILED;
+    return rsp_api::spmv_run(h, RSP_OPERATION_NON_TRANSPOSE, alpha, &t->child, d_x, beta, d_y, compute_type,
+                             d_buffer, 0);
+}
+
 rsp_status_t rsp_api::spmv_run(rsp_handle_t h, rsp_operation_t op, const void *alpha, rsp_spmat_t mat,
                                const void *d_x, const void *beta, void *d_y,
                                rsp_datatype_t compute_type, void *d_buffer, int part) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!mat || !alpha || !beta) return RSP_STATUS_INVALID_VALUE;
+    if (op == RSP_OPERATION_TRANSPOSE && part == 0)
+        return spmv_run_transposed(h, alpha, mat, d_x, beta, d_y, compute_type, d_buffer);
     if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
     if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
     if (mat->rows > 0 && (!d_y || (mat->cols > 0 && !d_x))) return RSP_STATUS_INVALID_VALUE;
@@ -573,6 +669,7 @@ rsp_status_t rsp_destroy_spmat(rsp_spmat_t mat) {
         (void)hipFree(mat->d_plan);
         (void)hipSetDevice(cur);
     }
+    delete mat->tside;  // (on the device it was built on)
     delete mat;
     return RSP_STATUS_SUCCESS;
 }
@@ -587,6 +684,14 @@ rsp_status_t rsp_spmv_buffer_size(rsp_handle_t h, rsp_operation_t op, const void
     return guarded([&] {
         if (!h) return RSP_STATUS_NOT_INITIALIZED;
         if (!mat || !buffer_size) return RSP_STATUS_INVALID_VALUE;
+        if (op == RSP_OPERATION_TRANSPOSE) {  // the transposed side, built if absent; no workspace either
+            if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
+            RSP_TRY(tside_ready(h, mat));
+            rsp_spmat *c = &mat->tside->child;
+            if (!c->planned || c->plan_type != compute_type) RSP_TRY(spmv_plan(h, c, compute_type));
+            *buffer_size = 0;
+            return RSP_STATUS_SUCCESS;
+        }
         if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
         if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
         // the schedule is built here, into the matrix's own device memory (the
@@ -609,9 +714,10 @@ rsp_status_t rsp_spmv_preprocess(rsp_handle_t h, rsp_operation_t op, const void 
     return guarded([&] {
         if (!h) return RSP_STATUS_NOT_INITIALIZED;
         if (!mat) return RSP_STATUS_INVALID_VALUE;
-        if (op != RSP_OPERATION_NON_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
+        if (op != RSP_OPERATION_NON_TRANSPOSE && op != RSP_OPERATION_TRANSPOSE) return RSP_STATUS_NOT_SUPPORTED;
         if (compute_type != mat->type) return RSP_STATUS_INVALID_VALUE;
-        return spmv_plan(h, mat, compute_type);  // explicit request: always re-plan
+        // explicit request: always re-plan (op = TRANSPOSE: the transposed side alone, from the pattern as it is now)
+        return op == RSP_OPERATION_TRANSPOSE ? tside_build(h, mat) : spmv_plan(h, mat, compute_type);
     });
 }
 
@@ -702,6 +808,53 @@ rsp_status_t rsp_scatter(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, c
     if (n < 0 || (n > 0 && (!d_idx || !d_src || !d_dst))) return RSP_STATUS_INVALID_VALUE;
     hipError_t e = rsp_k::scatter(value_type == RSP_R_64F ? 8 : 4, n, d_idx, d_src, d_dst, h->stream);
     return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+}
+
+rsp_status_t rsp_spmv_transpose_permute(rsp_handle_t h, rsp_spmat_t mat) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!mat) return RSP_STATUS_INVALID_VALUE;
+    const rsp_spmat_tside *t = mat->tside;
+    if (!t || t->child.type != mat->type) return RSP_STATUS_NOT_INITIALIZED;
+    if (t->child.nnz > 0 && !mat->vals) return RSP_STATUS_INVALID_VALUE;
+    const hipError_t e = rsp_k::permute_values((int)elem_size(mat->type), t->child.nnz, t->perm, mat->vals, t->vt.p,
+                                               h->num_cus, h->stream);
+    return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+}
+
+rsp_status_t rsp_csr2csc(rsp_handle_t h, int64_t rows, int64_t cols, int64_t nnz, const int *d_row_offsets,
+                         const int *d_col_ind, const void *d_values, rsp_datatype_t value_type,
+                         int *d_csc_col_offsets, int *d_csc_row_ind, void *d_csc_values) {
+    return guarded([&] {
+        if (!h) return RSP_STATUS_NOT_INITIALIZED;
+        if (rows < 0 || cols < 0 || nnz < 0 || rows > INT_MAX - 1 || cols > INT_MAX - 1 || nnz > INT_MAX)
+            return RSP_STATUS_INVALID_VALUE;
+        if (value_type != RSP_R_64F && value_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+        if ((!d_row_offsets && rows > 0) || !d_csc_col_offsets) return RSP_STATUS_INVALID_VALUE;
+        const bool symbolic = !d_values && !d_csc_values;
+        rsp_spmat a;  // (a view for transpose_pattern: the pattern alone)
+        memset(&a, 0, sizeof(a));
+        a.rows = rows;
+        a.cols = cols;
+        a.nnz = nnz;
+        a.rowptr = const_cast<int *>(d_row_offsets);
+        a.colidx = const_cast<int *>(d_col_ind);
+        HostTranspose ht;
+        RSP_TRY(transpose_pattern(h, &a, ht));
+        if (ht.nnz > 0 && (!d_csc_row_ind || (!symbolic && (!d_values || !d_csc_values))))
+            return RSP_STATUS_INVALID_VALUE;
+        DevMem perm;
+        RSP_CHECK_HIP(upload_ints(h, d_csc_col_offsets, ht.rowptr));
+        RSP_CHECK_HIP(upload_ints(h, d_csc_row_ind, ht.colidx));
+        if (!symbolic && ht.nnz > 0) {
+            RSP_CHECK_HIP(hipMalloc(&perm.p, (size_t)ht.nnz * sizeof(int)));
+            RSP_CHECK_HIP(upload_ints(h, perm.p, ht.perm));
+            if (rsp_k::permute_values((int)elem_size(value_type), ht.nnz, (const int *)perm.p, d_values,
+                                      d_csc_values, h->num_cus, h->stream) != hipSuccess)
+                return RSP_STATUS_EXECUTION_FAILED;
+        }
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));  // (ht and perm go on return)
+        return RSP_STATUS_SUCCESS;
+    });
 }
 
 rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,

@@ -4,6 +4,7 @@
 // few functions one unit calls in another (namespace rsp_api).
 //   rsp_api.cpp           handle, matrix descriptor, SpMV (plan upload, run, batch)
 //   spmv_plan.cpp         the SpMV planner (spmv_plan.h; no HIP calls)
+//   csr_transpose.cpp     the pattern transposer (csr_transpose.h; no HIP calls)
 //   api_ilu_analysis.cpp  ILU(0) analysis, the solve plans, the plan queries
 //   api_ilu_solve.cpp     factor and triangular solves, flow give-up recovery
 //   api_krylov.cpp        BiCGStab, GMRES, rsp_dot, rsp_orthogonalize
@@ -27,6 +28,7 @@
 #include "rsp_kernels.h"
 #include "ilu_analysis.h"
 #include "spmv_plan.h"
+#include "csr_transpose.h"
 
 struct rsp_context {
     int device;
@@ -55,6 +57,7 @@ struct rsp_context {
 // the reference's exact call sequence create_csr -> bufferSize -> malloc ->
 // 50x SpMV pays no planning inside a timed call, and any number of matrices
 // may share one workspace without re-planning.
+struct rsp_spmat_tside;
 struct rsp_spmat {
     int64_t rows, cols, nnz;
     int *rowptr;
@@ -75,6 +78,7 @@ struct rsp_spmat {
     int64_t local_cols;         // rsp_spmat_set_local_cols (-1: not split)
     int nint;                   // interior tiles at the front of the schedule
     unsigned long long plan_gen;  // unique per plan / value rebind (batch staleness key)
+    rsp_spmat_tside *tside;     // the transposed side, built by the first op = TRANSPOSE use (else null)
 };
 
 // A hipMalloc'ed allocation, freed with its owner (move-only).
@@ -88,6 +92,31 @@ struct DevMem {
     }
     ~DevMem() {
         if (p) (void)hipFree(p);
+    }
+};
+
+// What rsp_spmv(op = TRANSPOSE) keeps in a matrix: the CSR pattern of A^T in
+// the order of csr_transpose.h, the permutation that carries A's values into
+// it, the permuted values (refilled by every call) and a descriptor over them
+// whose schedule spmv_plan builds as for any matrix. Host-blocking to build
+// (rsp_api.cpp tside_build); freed on the device it was built on.
+struct rsp_spmat_tside {
+    int device = 0;
+    DevMem pattern;  // [t_rowptr (cols + 1) | t_colidx (nnz_s) | perm (nnz_s)], each 256-B aligned
+    DevMem vt;       // nnz_s values of child.type
+    int *perm = nullptr;
+    rsp_spmat child{};  // A^T: cols x rows over pattern and vt; its d_plan is freed here
+    rsp_spmat_tside() = default;
+    rsp_spmat_tside(const rsp_spmat_tside &) = delete;
+    rsp_spmat_tside &operator=(const rsp_spmat_tside &) = delete;
+    ~rsp_spmat_tside() {
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        (void)hipSetDevice(device);
+        if (child.d_plan) (void)hipFree(child.d_plan);
+        pattern = DevMem();
+        vt = DevMem();
+        (void)hipSetDevice(cur);
     }
 };
 

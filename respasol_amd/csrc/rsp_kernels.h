@@ -709,6 +709,11 @@ hipError_t scatter(int elem_bytes, int64_t n, const int64_t *idx, const void *sr
 hipError_t spmv_f64(const rsp::SpmvArgs &a, hipStream_t s);
 hipError_t spmv_batch_f64(const rsp::SpmvBatchArgs &a, hipStream_t s);
 int spmv_tiles_per_cu(int elem_bytes);  // resident spmv_tiles workgroups per CU
+// csr_transpose.hip: vt[k] = v[perm[k]] for k < nnz, elements moved as bits
+// (the values of A^T, perm from csr_transpose.h); nnz <= 0 launches nothing.
+hipError_t permute_values(int elem_bytes, int64_t nnz, const int *perm, const void *v, void *vt, int num_cus,
+                          hipStream_t s);
+void warm_transpose();
 // warm_*: load the translation unit's code object on the current device now
 // (HIP loads a code object at the first use of one of its kernels; without
 // this, the first timed call of a run pays it: ~1.2-1.5 ms, measured).

@@ -7,7 +7,14 @@ Mapping to the reference's cuSPARSE usage:
   SpMat                  cusparseCreateCsr + SpMV_bufferSize (builds the
                          schedule) + the caller's workspace cudaMalloc
                                                              (GPU/spmv.cu:148-164)
-  SpMat.spmv             cusparseSpMV                        (GPU/spmv.cu:184-186)
+  SpMat.spmv             cusparseSpMV                        (GPU/spmv.cu:184-186);
+                         transpose=True: op = CUSPARSE_OPERATION_TRANSPOSE, on a
+                         transposed side built on first use
+                         (SpMat.preprocess_transpose rebuilds it)
+  csr2csc                cusparseCsr2cscEx2: the CSR arrays of A^T in the order
+                         SpMat.spmv(transpose=True) uses (rsp_csr2csc)
+  csr_transpose_host     the same transpose of a host pattern, no device
+                         (rsp_csr_transpose_host)
   SpmvBatch              cusparseSpMV over several matrices as one launch (no
                          cuSPARSE counterpart; bits equal to SpMat.spmv each)
   Ilu0.analysis          csrilu02_analysis + 2x csrsv2_analysis (GPU/ilu0.cu:203-252)
@@ -125,16 +132,31 @@ class SpMat:
         return int(self.colidx.numel())
 
     def spmv(self, x: torch.Tensor, y: torch.Tensor | None = None, alpha: float = 1.0,
-             beta: float = 0.0) -> torch.Tensor:
-        """y = alpha*A*x + beta*y on the handle's stream (cusparseSpMV)."""
-        if x.dtype != self.dtype or x.numel() < self.n:
+             beta: float = 0.0, transpose: bool = False) -> torch.Tensor:
+        """y = alpha*A*x + beta*y on the handle's stream (cusparseSpMV), or with
+        transpose=True y = alpha*A^T*x + beta*y (x of m, y of n elements): the
+        first such call builds the matrix's transposed side (host-blocking),
+        and every one permutes the current values before the product."""
+        n_in, n_out = (self.m, self.n) if transpose else (self.n, self.m)
+        if x.dtype != self.dtype or x.numel() < n_in:
             raise ValueError("x has the wrong dtype or length")
         if y is None:
-            y = torch.empty(self.m, dtype=self.dtype, device=x.device)
+            y = torch.empty(n_out, dtype=self.dtype, device=x.device)
+        elif transpose and (y.dtype != self.dtype or y.numel() < n_out):
+            raise ValueError("y has the wrong dtype or length")
         a, b = _scalar(alpha, self.dtype), _scalar(beta, self.dtype)
-        check(rsp.rsp_spmv(self.handle.ptr, _lib.OP_N, C.byref(a), self._mat, _ptr(x), C.byref(b),
-                           _ptr(y), _DT[self.dtype], _ptr(self.buffer)), "rsp_spmv")
+        check(rsp.rsp_spmv(self.handle.ptr, _lib.OP_T if transpose else _lib.OP_N, C.byref(a), self._mat,
+                           _ptr(x), C.byref(b), _ptr(y), _DT[self.dtype], _ptr(self.buffer)), "rsp_spmv")
         return y
+
+    def preprocess_transpose(self) -> None:
+        """Rebuild the transposed side from the pattern arrays as they are now
+        (rsp_spmv_preprocess, op = TRANSPOSE; host-blocking). Only needed after
+        the pattern changed in place: spmv(transpose=True) builds it on first use."""
+        one, zero = _scalar(1.0, self.dtype), _scalar(0.0, self.dtype)
+        check(rsp.rsp_spmv_preprocess(self.handle.ptr, _lib.OP_T, C.byref(one), self._mat, None,
+                                      C.byref(zero), None, _DT[self.dtype], _ptr(self.buffer)),
+              "rsp_spmv_preprocess")
 
     def bind(self, x: torch.Tensor, y: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
         """The call y = alpha*A*x + beta*y with its C arguments converted once:
@@ -536,5 +558,45 @@ def scatter(handle: Handle, idx: torch.Tensor, src: torch.Tensor, dst: torch.Ten
           "rsp_scatter")
 
 
+def csr2csc(handle: Handle, rowptr: torch.Tensor, colidx: torch.Tensor, values: torch.Tensor | None,
+            n_cols: int):
+    """The CSR arrays (rowptr, colidx, values) of A^T — A's CSC form — as three
+    new device tensors, in the order SpMat.spmv(transpose=True) uses
+    (rsp_csr2csc; host-blocking). values=None: the pattern only, and None is
+    returned for the values."""
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32:
+        raise TypeError("rowptr/colidx must be int32 (CUSPARSE_INDEX_32I)")
+    if values is not None and values.dtype not in _DT:
+        raise TypeError("values must be float64 or float32")
+    m = rowptr.numel() - 1
+    nnz = int(rowptr[-1].item()) if m > 0 else 0  # (host-blocking anyway)
+    if nnz > colidx.numel() or (values is not None and nnz > values.numel()):
+        raise ValueError("colidx / values are shorter than the pattern")
+    t_rp = torch.empty(int(n_cols) + 1, dtype=torch.int32, device=rowptr.device)
+    t_ci = torch.empty(nnz, dtype=torch.int32, device=rowptr.device)
+    t_va = None if values is None else torch.empty(nnz, dtype=values.dtype, device=rowptr.device)
+    check(rsp.rsp_csr2csc(handle.ptr, m, int(n_cols), colidx.numel(), _ptr(rowptr), _ptr(colidx), _ptr(values),
+                          _DT[values.dtype] if values is not None else _lib.R_64F, _ptr(t_rp), _ptr(t_ci),
+                          _ptr(t_va)), "rsp_csr2csc")
+    return t_rp, t_ci, t_va
+
+
+def csr_transpose_host(rowptr, colidx, n_cols: int):
+    """(t_rowptr, t_colidx, perm) of a HOST pattern (rsp_csr_transpose_host; no
+    device needed): the CSR pattern of A^T and, for each of its entries, the
+    index of the entry of A it is."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    m = len(rp) - 1
+    nnz = max(int(rp[-1]), 0) if m > 0 else 0
+    if nnz > len(ci):
+        raise ValueError("colidx is shorter than the pattern")
+    t_rp = np.zeros(int(n_cols) + 1, np.int32)
+    t_ci, perm = np.zeros(nnz, np.int32), np.zeros(nnz, np.int32)
+    check(rsp.rsp_csr_transpose_host(m, int(n_cols), rp.ctypes.data, ci.ctypes.data, t_rp.ctypes.data,
+                                     t_ci.ctypes.data, perm.ctypes.data), "rsp_csr_transpose_host")
+    return t_rp, t_ci, perm
+
+
 __all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "GMRES", "SolveResult", "dot", "orthogonalize", "upload_csr",
-           "gather", "scatter", "RspError"]
+           "gather", "scatter", "csr2csc", "csr_transpose_host", "RspError"]
