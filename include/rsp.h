@@ -513,11 +513,58 @@ rsp_status_t rsp_ilu0_solve_blocks(rsp_ilu0_info_t info, int *blocks_lower, int 
  * symbolic factor, factor and solve plans. Returns the level counts, a 64-bit
  * digest of every array built (equal to rsp_ilu0_plan_digest of a device
  * analysis of the same pattern, whatever runs where) and, if phase_ms is not
- * NULL, the wall time of its 6 phases in ms. Same status codes as the
+ * NULL, the wall time of its 6 phases in ms. The slot layout's budget is
+ * RSP_ILU_SLOT_CAP_MB as in the analysis, else 2 GB. Same status codes as the
  * analysis (INVALID_VALUE for a malformed or unsorted pattern). */
 rsp_status_t rsp_ilu0_analysis_host(int n, const int *row_offsets, const int *col_ind,
                                     int *levels_lower, int *levels_upper, uint64_t *digest,
                                     double *phase_ms);
+/* Tests (no cuSPARSE counterpart, no device needed): the level plans of the
+ * same host phases — the L, L^T and U solve plans and the factor plan —
+ * checked and counted. The slot layout's budget is RSP_ILU_SLOT_CAP_MB if the
+ * environment sets it, else rsp_ilu0_analysis_host's.
+ * The check (INTERNAL_ERROR if it fails; the first violation goes to stderr),
+ * per solve plan: every row is one task, in level order, a level's short rows
+ * before its wave rows before its hub rows; a task's flat terms are its row's
+ * terms in the solve's order, pad terms only where a thin row's term groups
+ * end; a thin level's term reads the y window slot of a producer that lies
+ * earlier in the run and at most 4096 slots before the end of the consumer's
+ * level, or is staged once in its own chunk and produced before that chunk;
+ * chunks tile their run within 1024 rows and 4096 terms; every thin row
+ * record decodes to its task (16-bit halves included); flow items cover each
+ * level's rows once, in order, short groups of 1 to 64 rows, with the gate
+ * the gate distance defines. Factor plan: every position of a thin level's
+ * rows is an item of one chunk once, within the chunk budgets, its pair
+ * start | count << 16 intact; a slot level's rm <= 256 and qm <= 1024 cover
+ * its rows, slots do not overlap and end within slot_total <= the budget; a
+ * flow run holds only slot levels without global-path rows, its items' rm |
+ * qm << 16 and offsets the level's.
+ * facts[0 .. nfacts): RSP_ILU_PLAN_FACTS values (less are cut, more are 0).
+ * Three blocks of 26 for the L, L^T and U DAG (d = 0, 26, 52):
+ *   d+0 levels; d+1 term group (2 / 4); d+2 thin segments; d+3 fat segments
+ *   launched level by level; d+4 flow segments; d+5 thin chunks; d+6 / d+7
+ *   most rows / flat terms of a chunk; d+8 staged terms; d+9 window terms;
+ *   d+10 slots of the longest thin run; d+11 / d+12 thin short / wave rows;
+ *   d+13 / d+14 / d+15 fat short / wave / hub rows; flow items: d+16 of 64
+ *   short rows, d+17 of 1 to 63 short rows (d+21: of those, of one row),
+ *   d+18 of one wave or hub row; d+19 levels in the padded short-row layout;
+ *   d+20 most padded terms of a thin level; d+22 / d+23 thin / fat levels;
+ *   d+24 flow items with a gate; d+25 levels of the longest flow segment.
+ * Then the factor (q = 78): q+0 fac_one (one level: no update pairs); q+1
+ *   fac_scale (one scaling launch, no plan: the rest is 0); q+2 thin
+ *   segments; q+3 fat levels; q+4 of them in the slot layout; q+5 / q+6 fat
+ *   levels the padding rule / the budget kept off it; q+7 fat levels' rows on the
+ *   global path (> 256 entries or > 1024 update pairs); q+8 flow runs; q+9 levels in
+ *   them; q+10 thin chunks; q+11 .. q+14 most items / pairs / staged values /
+ *   rounds of a chunk; q+15 most update pairs of one position in a thin
+ *   level; q+16 / q+17 most entries / update pairs of a fat level's row within those limits (rm / qm); q+18 slot_total
+ *   (ints); q+19 factor levels; q+20 most positions of a thin level; q+21
+ *   fewest positions of a fat level; q+22 thin levels; q+23 fat levels with
+ *   global-path rows; q+24 thin levels that hold such a row (hub levels);
+ *   q+25 most rows of a thin level. */
+#define RSP_ILU_PLAN_FACTS 104
+rsp_status_t rsp_ilu0_plan_facts_host(int n, const int *row_offsets, const int *col_ind, int64_t *facts,
+                                      int nfacts);
 /* Tests (no cuSPARSE counterpart, no device needed): the SpMV schedule
  * rsp_spmv_buffer_size builds (tiles, 16-bit column offsets, staged tiles'
  * column runs) for HOST arrays (base 0, m rows, compute type fp64 / fp32),

@@ -60,6 +60,7 @@ SOLVE_BREAKDOWN = 2
 KRY_CHUNK = 2048
 KRY_MAX_GRID = 1024
 GMRES_MAX_RESTART = 64  # RSP_GMRES_MAX_RESTART
+ILU_PLAN_FACTS = 104 # RSP_ILU_PLAN_FACTS
 
 MM_FULL_SYMMETRIC = 0x1
 MM_QUIET = 0x2
@@ -139,6 +140,7 @@ RSP_PROTOS = {
     "rsp_spmv_batch_info": (i32, [vp, vp, vp]),
     "rsp_spmv_plan_info": (i32, [vp, vp, vp]),
     "rsp_ilu0_analysis_host": (i32, [i32, vp, vp, vp, vp, vp, vp]),
+    "rsp_ilu0_plan_facts_host": (i32, [i32, vp, vp, vp, i32]),
     "rsp_spmv_plan_host": (i32, [i32, vp, vp, C.c_int64, i32, vp, vp, vp]),
     "rsp_spmv_plan_stats": (i32, [i32, vp, vp, C.c_int64, i32, vp]),
     "rsp_ilu0_plan_digest": (i32, [vp, vp]),

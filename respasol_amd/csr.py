@@ -180,3 +180,30 @@ def partition_rows(rowptr: np.ndarray, parts: int) -> np.ndarray:
                                bounds.ctypes.data_as(C.POINTER(C.c_int))) != 0:
         raise ValueError("partition_rows: bad arguments")
     return bounds
+
+
+_DAG_FACTS = ("levels", "group", "thin_segs", "fat_segs", "flow_segs", "chunks", "chunk_rows", "chunk_terms",
+              "staged", "window", "run_slots", "thin_short", "thin_wave", "fat_short", "fat_wave", "fat_hub",
+              "items_64", "items_part", "items_wave", "padded_levels", "thin_level_terms", "items_1",
+              "thin_levels", "fat_levels", "items_gated", "flow_seg_levels")
+_FACTOR_FACTS = ("fac_one", "fac_scale", "thin_segs", "fat_levels", "slot_levels", "pad_refused", "budget_refused",
+                 "global_rows", "flow_runs", "flow_levels", "chunks", "chunk_items", "chunk_pairs", "chunk_staged",
+                 "chunk_rounds", "item_pairs", "rm", "qm", "slot_total", "levels", "thin_level_items",
+                 "fat_level_items", "thin_levels", "global_levels", "hub_levels", "thin_level_rows")
+
+
+def ilu0_plan_facts(rowptr: np.ndarray, colidx: np.ndarray) -> dict:
+    """The level plans of the ILU(0) host analysis of a pattern (base 0),
+    checked and counted (rsp_ilu0_plan_facts_host, no device): {"L": {...},
+    "LT": {...}, "U": {...}, "F": {...}} by the names above, in the order of
+    include/rsp.h. Raises if the planner's own check of its plans fails."""
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    f = np.zeros(_lib.ILU_PLAN_FACTS, np.int64)
+    st = _lib.rsp.rsp_ilu0_plan_facts_host(rp.shape[0] - 1, rp.ctypes.data, ci.ctypes.data, f.ctypes.data, f.size)
+    if st != 0:
+        raise RuntimeError(f"rsp_ilu0_plan_facts_host: {_lib.rsp.rsp_get_error_string(st).decode()}")
+    nd = len(_DAG_FACTS)
+    out = {k: dict(zip(_DAG_FACTS, map(int, f[nd * j:nd * (j + 1)]))) for j, k in enumerate(("L", "LT", "U"))}
+    out["F"] = dict(zip(_FACTOR_FACTS, map(int, f[3 * nd:])))
+    return out

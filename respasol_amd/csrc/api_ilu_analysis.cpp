@@ -213,6 +213,11 @@ static long long slot_cap_ints() {
     }
     return cap_mb * (1LL << 20) / 4;
 }
+// ... of the host entries (no device to ask): the knob if set, else 2 GB
+static long long host_slot_cap_ints() {
+    const long long cap_mb = env_int("RSP_ILU_SLOT_CAP_MB", -1);
+    return (cap_mb >= 0 ? cap_mb : 2048) * (1LL << 20) / 4;
+}
 
 // The data-parallel analysis on the device (ilu_analysis.hip), overlapped
 // with the host level sets: validation, diagonal positions and structural
@@ -768,10 +773,31 @@ rsp_status_t rsp_ilu0_analysis_host(int n, const int *row_offsets, const int *co
             for (int i = 0; i < rsp_an::kPhases; i++) phase_ms[i] = 0.0;
         ph.start();
         rsp_an::IluHostPlan hp;
-        RSP_TRY(rsp_an::plan_host(n, row_offsets, col_ind, 1LL << 29, false, hp, ph));
+        RSP_TRY(rsp_an::plan_host(n, row_offsets, col_ind, host_slot_cap_ints(), false, hp, ph));
         if (levels_lower) *levels_lower = (int)hp.L.ptr.size() - 1;
         if (levels_upper) *levels_upper = (int)hp.LT.ptr.size() - 1;
         if (digest) *digest = rsp_an::digest(hp);
+        return RSP_STATUS_SUCCESS;
+    });
+}
+
+rsp_status_t rsp_ilu0_plan_facts_host(int n, const int *row_offsets, const int *col_ind, int64_t *facts, int nfacts) {
+    return guarded([&] {
+        if (nfacts < 0 || (nfacts > 0 && !facts)) return RSP_STATUS_INVALID_VALUE;
+        rsp_an::Phases ph;
+        ph.n = n;
+        ph.start();
+        const long long cap = host_slot_cap_ints();
+        rsp_an::IluHostPlan hp;
+        RSP_TRY(rsp_an::plan_host(n, row_offsets, col_ind, cap, true, hp, ph));
+        const std::string why = rsp_an::check_plans(row_offsets, col_ind, hp, cap);
+        if (!why.empty()) {
+            fprintf(stderr, "rsp_ilu0_plan_facts_host n=%d: %s\n", n, why.c_str());
+            return RSP_STATUS_INTERNAL_ERROR;
+        }
+        long long f[rsp_an::kPlanFacts];
+        rsp_an::plan_facts(row_offsets, hp, cap, f);
+        for (int k = 0; k < nfacts; k++) facts[k] = k < rsp_an::kPlanFacts ? (int64_t)f[k] : 0;
         return RSP_STATUS_SUCCESS;
     });
 }

@@ -11,6 +11,8 @@
 
 #include <stdint.h>
 
+#include <string>
+
 #include "rsp.h"
 #include "host_pool.h"
 #include "rsp_kernels.h"
@@ -180,6 +182,14 @@ bool plan_blocks(int kind, const int *rp, const int *ci, const IluHostPlan &hp, 
 void plan_u(const int *rp, const int *ci, IluHostPlan &hp);
 // 64-bit digest (FNV-1a) of every array of the plan (tests: identical plans).
 uint64_t digest(const IluHostPlan &hp);
+// Tests (ilu_plan_check.cpp; rsp_ilu0_plan_facts_host): whether the L, L^T,
+// U (where planned) and factor plans are valid — what the kernels rely on,
+// restated from the pattern and the level sets: "" or the first violation.
+// slot_cap: the budget plan_host was given. plan_facts: the counts rsp.h
+// documents (kPlanFacts values: three solve DAGs, then the factor).
+std::string check_plans(const int *rp, const int *ci, const IluHostPlan &hp, long long slot_cap);
+constexpr int kFactsPerDag = 26, kFactsFactor = 26, kPlanFacts = 3 * kFactsPerDag + kFactsFactor;
+void plan_facts(const int *rp, const IluHostPlan &hp, long long slot_cap, long long *facts);
 
 // ---- internal: shared by the analysis' own units (ilu_analysis.cpp,
 // ilu_plan_solve.cpp, ilu_plan_factor.cpp), not for its callers
