@@ -339,6 +339,54 @@ rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s);
 rsp_status_t rsp_dot(rsp_handle_t handle, rsp_datatype_t value_type, int64_t n, const void *d_x,
                      const void *d_y, double *result);
 
+/* ------------------- preconditioned conjugate gradients (CG), for SPD systems
+ *
+ * For a symmetric positive definite A, with M = L U as in rsp_bicgstab_* (or
+ * M = I). T is the iteration type (A's value type), P <= T the preconditioner
+ * type. A's symmetry is not verified: the caller is trusted, and a matrix or
+ * preconditioner that is not positive definite ends in BREAKDOWN.
+ *
+ *   set-up:  r = b - A x0
+ *   it = 1, 2, ...:
+ *       z = M^-1 r                        (M = I: z is r, nothing is copied)
+ *       rho' = (r,z)                      BREAKDOWN if rho' <= 0 or not finite
+ *       p = z               if it == 1
+ *       p = z + T(beta) p   otherwise     beta = rho'/rho in fp64, rounded to T once
+ *       q = A p
+ *       alpha = rho'/(p,q) in fp64        BREAKDOWN if (p,q) <= 0 or not finite
+ *       x = x + T(alpha) p;  r = r - T(alpha) q
+ *
+ * The plain (Fletcher-Reeves) beta: the Polak-Ribiere form costs one more
+ * vector and dot and recovers none of the iterations an fp32 preconditioner
+ * adds. All dots are fp64 whatever T; vectors are stored in T.
+ * Per iteration: one rsp_spmv, two triangular solves and four kernels of the
+ * solver's own (five with a narrower preconditioner: the widening of its
+ * result; three and no solve when M = I); the scalars stay on the device.
+ * Memory: 4 vectors of T (3 when M = I) plus the apply's buffers.
+ * Deterministic as rsp_bicgstab_*. */
+typedef struct rsp_cg *rsp_cg_t;
+/* As rsp_bicgstab_create: the same arguments, checks and statuses (ZERO_PIVOT
+ * included). All vectors are allocated here. */
+rsp_status_t rsp_cg_create(rsp_handle_t handle, rsp_spmat_t A, rsp_ilu0_info_t info,
+                           rsp_datatype_t precond_type, const void *d_factor, rsp_cg_t *s);
+/* Solves A x = b; arguments, the stopping test, the checks, INVALID_VALUE and
+ * EXECUTION_FAILED as rsp_bicgstab_solve. *relres = ||r|| / ||b|| of the
+ * recurrence residual at the last check; check_every changes no bit of x for
+ * a given iteration count.
+ *   - b = 0, an x0 inside rtol, a non-finite b / x0: as rsp_bicgstab_solve.
+ *   - BREAKDOWN: (r,z) or (p,q) was <= 0 or not finite (M or A is not positive
+ *     definite), detected on the device before the iteration wrote x or r:
+ *     they keep the values of the last completed iteration, *iters counts
+ *     those, no NaN reaches x.
+ *   - r == 0 exactly is CONVERGED (also at rtol = 0), at the first check that
+ *     sees it, with *iters = the iteration that reached it. */
+rsp_status_t rsp_cg_solve(rsp_handle_t handle, rsp_cg_t s, const void *d_b, void *d_x, double rtol,
+                          int max_iters, int check_every, int *iters, double *relres,
+                          rsp_solve_reason_t *reason);
+/* The value of each check of the last solve, as rsp_bicgstab_history. */
+rsp_status_t rsp_cg_history(rsp_cg_t s, int cap, double *relres, int *count);
+rsp_status_t rsp_cg_destroy(rsp_cg_t s);
+
 /* -------------------------------------- restarted flexible GMRES(m) (FGMRES)
  *
  * The second Krylov method on the same operator set: right-preconditioned

@@ -123,6 +123,10 @@ RSP_PROTOS = {
     "rsp_bicgstab_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),
     "rsp_bicgstab_destroy": (i32, [vp]),
     "rsp_dot": (i32, [vp, i32, i64, vp, vp, C.POINTER(C.c_double)]),
+    "rsp_cg_create": (i32, [vp, vp, vp, i32, vp, C.POINTER(vp)]),
+    "rsp_cg_solve": (i32, [vp, vp, vp, vp, C.c_double, i32, i32, ip, C.POINTER(C.c_double), ip]),
+    "rsp_cg_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),
+    "rsp_cg_destroy": (i32, [vp]),
     "rsp_gmres_create": (i32, [vp, vp, vp, i32, vp, i32, C.POINTER(vp)]),
     "rsp_gmres_solve": (i32, [vp, vp, vp, vp, C.c_double, i32, i32, ip, C.POINTER(C.c_double), ip]),
     "rsp_gmres_history": (i32, [vp, i32, C.POINTER(C.c_double), ip]),

@@ -1,8 +1,8 @@
 // api_krylov.cpp — the Krylov solvers of include/rsp.h: ILU(0)-preconditioned
-// BiCGStab and restarted flexible GMRES(m), and the two building blocks they
-// expose (rsp_dot, rsp_orthogonalize, rsp_gmres_lsq_host). Host loops over the
-// kernels of krylov.hip, spmv_run (rsp_api.cpp) and the triangular solves
-// (api_ilu_solve.cpp); what the two solvers share is KrylovCommon.
+// BiCGStab, preconditioned CG and restarted flexible GMRES(m), and the building
+// blocks they expose (rsp_dot, rsp_orthogonalize, rsp_gmres_lsq_host). Host
+// loops over the kernels of krylov.hip, spmv_run (rsp_api.cpp) and the
+// triangular solves (api_ilu_solve.cpp); what the solvers share is KrylovCommon.
 
 #include "rsp_internal.h"
 
@@ -321,6 +321,125 @@ static rsp_status_t krylov_dot(rsp_handle_t h, rsp_datatype_t value_type, int64_
     return RSP_STATUS_SUCCESS;
 }
 
+/* ------------------------------------------------------------------- CG */
+
+// One solver: r, p, q and, with M, z (type T); the scalar / partial block and
+// the pinned mirror are BiCGStab's.
+struct rsp_cg : KrylovCommon {
+    void *r = nullptr, *p = nullptr, *q = nullptr;
+    void *z = nullptr;  // M = I: r itself
+};
+
+static rsp_status_t cg_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
+                              const void *d_factor, rsp_cg_t *out) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!out) return RSP_STATUS_INVALID_VALUE;
+    *out = nullptr;
+    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor));
+    std::unique_ptr<rsp_cg> s(new rsp_cg);  // (a half-built solver is freed on every way out)
+    krylov_bind(*s, h, A, info, precond_type, d_factor);
+    const size_t tb = s->tbytes();
+    const int nt = info ? 4 : 3;
+    char *at = nullptr;
+    RSP_TRY(krylov_alloc(*s, align256(rsp::kKryBlockDoubles * sizeof(double)), nt * tb,
+                         rsp::kKryScalars + 2 * (size_t)rsp::kKryMaxGrid, &at));
+    void **tv[] = {&s->r, &s->p, &s->q, &s->z};
+    for (int k = 0; k < nt; k++, at += tb) *tv[k] = at;
+    if (!info) s->z = s->r;
+    *out = s.release();
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t cg_solve(rsp_handle_t h, rsp_cg_t s, const void *d_b, void *d_x, double rtol, int max_iters,
+                             int check_every, int *iters, double *relres, rsp_solve_reason_t *reason) {
+    RSP_TRY(krylov_solve_begin(h, s, d_b, d_x, rtol, max_iters, check_every, iters, relres, reason));
+    s->history.reserve((size_t)max_iters / check_every + 2);
+    const int type = s->kry_type();
+    const bool ftz = h->ftz != 0 && type != rsp::kKryF64;
+    const int G = rsp::kry_grid(s->n).grid;
+    rsp::KryArgs a{};
+    a.n = s->n;
+    a.blk = s->d_blk;
+    a.b = d_b;
+    a.x = d_x;
+    a.r = s->r;
+    a.z = s->z;
+    a.p = s->p;
+    a.v = s->q;
+    a.copy32 = s->mixed() ? s->pin : nullptr;
+    auto kern = [&](rsp::KryOp op) {
+        const hipError_t e = ftz ? rsp_k_ftz::krylov(op, type, a, h->stream) : rsp_k::krylov(op, type, a, h->stream);
+        return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+    };
+    // the one host wait of an iteration, as bicgstab_solve's
+    double *hp = s->h_pin;
+    auto read_back = [&]() -> rsp_status_t {
+        RSP_CHECK_HIP(hipMemcpyAsync(hp, s->d_blk, (rsp::kKryScalars + (size_t)G) * sizeof(double),
+                                     hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipEventRecord(s->ev, h->stream));
+        RSP_CHECK_HIP(hipEventSynchronize(s->ev));
+        return RSP_STATUS_SUCCESS;
+    };
+    // r = b - A x0 (mixed: and its fp32 copy), (b,b), (r,r)
+    RSP_TRY(krylov_spmv(h, *s, d_x, s->q));
+    RSP_TRY(kern(rsp::kKryCgInit));
+    RSP_CHECK_HIP(hipMemcpyAsync(hp + rsp::kKryScalars + rsp::kKryMaxGrid,
+                                 s->d_blk + rsp::kKryScalars + (size_t)rsp::kKryPartBB * rsp::kKryMaxGrid,
+                                 (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RSP_TRY(read_back());
+    const double bb = rsp::kry_combine_host(hp + rsp::kKryScalars + rsp::kKryMaxGrid, G);
+    double rr = rsp::kry_combine_host(hp + rsp::kKryScalars, G);
+    const double bnorm = sqrt(bb);
+    if (bb == 0.0) {  // x = 0 solves it
+        RSP_TRY(kern(rsp::kKryZero));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        *reason = RSP_SOLVE_CONVERGED;
+        return RSP_STATUS_SUCCESS;
+    }
+    if (!std::isfinite(bb) || !std::isfinite(rr)) {  // b or x0 not finite: nothing to iterate on
+        *relres = sqrt(rr) / bnorm;
+        *reason = RSP_SOLVE_BREAKDOWN;
+        return RSP_STATUS_SUCCESS;
+    }
+    double rel = sqrt(rr) / bnorm;
+    *relres = rel;
+    int done = 0;
+    if (rel <= rtol) {
+        *reason = RSP_SOLVE_CONVERGED;
+    } else {
+        for (int it = 1; it <= max_iters; it++) {
+            a.it = it;
+            if (s->info) {
+                RSP_TRY(krylov_apply(h, *s, s->r, s->z, ftz));
+                RSP_TRY(kern(rsp::kKryCgDotRZ));
+            }
+            RSP_TRY(kern(rsp::kKryCgPUpdate));
+            RSP_TRY(krylov_spmv(h, *s, s->p, s->q));
+            RSP_TRY(kern(rsp::kKryCgDotPQ));
+            RSP_TRY(kern(rsp::kKryCgXUpdate));
+            done = it;
+            if (it % check_every != 0 && it != max_iters) continue;
+            RSP_TRY(read_back());
+            rr = rsp::kry_combine_host(hp + rsp::kKryScalars, G);
+            rel = sqrt(rr) / bnorm;
+            const int flag = (int)hp[rsp::kKryFlag];
+            if (flag) done = (int)hp[rsp::kKryFlagIt] - 1;  // x and r stand as that iteration found them
+            s->history.push_back(rel);
+            if (rel <= rtol) {  // (before the flag: r == 0 exactly is flagged by the next iteration's rho)
+                *reason = RSP_SOLVE_CONVERGED;
+                break;
+            }
+            if (flag) {
+                *reason = RSP_SOLVE_BREAKDOWN;
+                break;
+            }
+        }
+    }
+    *iters = done;
+    *relres = rel;
+    return krylov_solve_end(h, *s, done);
+}
+
 /* ------------------------------------------------ FGMRES + orthogonalize */
 
 // One solver: the basis V (m + 1 columns), w and Z (m columns, with M), the
@@ -555,6 +674,26 @@ rsp_status_t rsp_bicgstab_destroy(rsp_bicgstab_t s) {
 rsp_status_t rsp_dot(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, const void *d_x, const void *d_y,
                      double *result) {
     return guarded([&] { return krylov_dot(h, value_type, n, d_x, d_y, result); });
+}
+
+rsp_status_t rsp_cg_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
+                           const void *d_factor, rsp_cg_t *s) {
+    return guarded([&] { return cg_create(h, A, info, precond_type, d_factor, s); });
+}
+
+rsp_status_t rsp_cg_solve(rsp_handle_t h, rsp_cg_t s, const void *d_b, void *d_x, double rtol, int max_iters,
+                          int check_every, int *iters, double *relres, rsp_solve_reason_t *reason) {
+    return guarded([&] { return cg_solve(h, s, d_b, d_x, rtol, max_iters, check_every, iters, relres, reason); });
+}
+
+rsp_status_t rsp_cg_history(rsp_cg_t s, int cap, double *relres, int *count) {
+    return krylov_history(s, cap, relres, count);
+}
+
+rsp_status_t rsp_cg_destroy(rsp_cg_t s) {
+    if (!s) return RSP_STATUS_INVALID_VALUE;
+    delete s;
+    return RSP_STATUS_SUCCESS;
 }
 
 rsp_status_t rsp_gmres_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,

@@ -1,7 +1,7 @@
 // krylov.hip — the vector side of the ILU(0)-preconditioned BiCGStab iteration
-// (rsp_bicgstab_*), of restarted flexible GMRES (rsp_gmres_*,
-// rsp_orthogonalize: the gm_* kernels, described where they start) and rsp_dot,
-// for gfx950. The SpMVs and triangular solves of an iteration are the library's
+// (rsp_bicgstab_*), of preconditioned CG (rsp_cg_*: the cg_* kernels) and of
+// restarted flexible GMRES (rsp_gmres_*, rsp_orthogonalize: the gm_* kernels),
+// both described where they start, and rsp_dot, for gfx950. The SpMVs and triangular solves of an iteration are the library's
 // existing entry points; everything between them is here. BiCGStab, five
 // launches per iteration:
 //
@@ -375,6 +375,144 @@ __global__ __launch_bounds__(kKryThreads) void kry_dot(long long n, long long ch
     put_partial(blk, kKryPartRR, block_sum(acc, lds));
 }
 
+// ------------------------------------------------------------------- CG
+//
+// Preconditioned conjugate gradients (rsp_cg_*) for a symmetric positive
+// definite A, M = L U as above. An iteration is four launches after the apply
+// that leaves z = M^-1 r (three when M = I: z is r, and (r,z) is the (r,r) the
+// x-update left):
+//
+//   cg_dot<RZ>   (r,z)
+//   cg_p_update  rho' = (r,z); beta = rho'/rho; p = z + beta p     (it = 1: p = z)
+//                                                    -- the SpMV: v = A p --
+//   cg_dot<PQ>   (p,v)
+//   cg_x_update  alpha = rho'/(p,v); x += alpha p; r -= alpha v [+ fp32 copy]; (r,r)
+//
+// rho lives in the two parity slots as BiCGStab's: cg_p_update reads the other
+// parity's and writes its own, cg_x_update reads that one. Breakdown: rho' or
+// (p,v) that is <= 0 or not finite (M or A not positive definite; rho' = 0 is
+// also r = 0, which the host's rel <= rtol test sees first) stores a code in
+// kKryFlag before anything is written, as above.
+
+__device__ __forceinline__ bool not_positive(double d) { return !(d > 0.0) || !__builtin_isfinite(d); }
+
+template <typename T, bool VEC, bool COPY>
+__global__ __launch_bounds__(kKryThreads) void cg_init(long long n, long long chunk, double *blk,
+                                                       const T *__restrict__ b, const T *__restrict__ v,
+                                                       T *__restrict__ r, float *__restrict__ copy32) {
+    __shared__ double lds[kKryThreads / 64];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        blk[kKryRho0] = 1.0;
+        blk[kKryRho1] = 1.0;
+        blk[kKryAlpha] = 1.0;
+        blk[kKryOmega] = 1.0;
+        blk[kKryFlag] = 0.0;
+        blk[kKryFlagIt] = 0.0;
+    }
+    double bb = 0.0, rr = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> gb = ld<T, VEC>(b, j, cnt), gv = ld<T, VEC>(v, j, cnt);
+        Grp<T> gr;
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) {
+            gr.e[k] = gb.e[k] - gv.e[k];
+            if (k < cnt) {
+                bb += (double)gb.e[k] * (double)gb.e[k];
+                rr += (double)gr.e[k] * (double)gr.e[k];
+            }
+        }
+        st<T, VEC>(r, j, cnt, gr);
+        if constexpr (COPY) st_copy32<VEC>(copy32, j, cnt, gr);
+    }
+    bb = block_sum(bb, lds);
+    rr = block_sum(rr, lds);
+    put_partial(blk, kKryPartBB, bb);
+    put_partial(blk, kKryPartRR, rr);
+}
+
+template <typename T, bool VEC, int PART>
+__global__ __launch_bounds__(kKryThreads) void cg_dot(long long n, long long chunk, double *blk,
+                                                      const T *__restrict__ x, const T *__restrict__ y) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    double acc = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        const Grp<T> ga = ld<T, VEC>(x, j, cnt), gb = ld<T, VEC>(y, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++)
+            if (k < cnt) acc += (double)ga.e[k] * (double)gb.e[k];
+    }
+    put_partial(blk, PART, block_sum(acc, lds));
+}
+
+// z and p may not alias; z == r (M = I) is read only here. part: where rho' is.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kKryThreads) void cg_p_update(long long n, long long chunk, double *blk, int it,
+                                                           int part, const T *__restrict__ z, T *__restrict__ p) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    const double rho = combine(blk, part, lds);
+    if (not_positive(rho)) {
+        set_break(blk, kKryBreakCgRZ, it);
+        return;
+    }
+    double beta = 0.0;
+    if (it > 1) {
+        beta = rho / blk[(it & 1) ? kKryRho0 : kKryRho1];  // (the old rho passed this test an iteration ago)
+        if (!__builtin_isfinite(beta)) {
+            set_break(blk, kKryBreakCgRZ, it);
+            return;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) blk[(it & 1) ? kKryRho1 : kKryRho0] = rho;
+    const T tb = (T)beta;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> gp = ld<T, VEC>(z, j, cnt);
+        if (it > 1) {
+            const Grp<T> go = ld<T, VEC>(p, j, cnt);
+#pragma unroll
+            for (int k = 0; k < Grp<T>::V; k++) gp.e[k] = gp.e[k] + tb * go.e[k];
+        }
+        st<T, VEC>(p, j, cnt, gp);
+    }
+}
+
+template <typename T, bool VEC, bool COPY>
+__global__ __launch_bounds__(kKryThreads) void cg_x_update(long long n, long long chunk, double *blk, int it,
+                                                           T *__restrict__ x, T *__restrict__ r,
+                                                           const T *__restrict__ p, const T *__restrict__ q,
+                                                           float *__restrict__ copy32) {
+    __shared__ double lds[kKryThreads / 64];
+    if (broken(blk, lds)) return;
+    const double pq = combine(blk, kKryPartPQ, lds);
+    if (not_positive(pq)) {
+        set_break(blk, kKryBreakCgPQ, it);
+        return;
+    }
+    const double alpha = blk[(it & 1) ? kKryRho1 : kKryRho0] / pq;
+    if (!__builtin_isfinite(alpha)) {
+        set_break(blk, kKryBreakCgPQ, it);
+        return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) blk[kKryAlpha] = alpha;
+    const T ta = (T)alpha;
+    double rr = 0.0;
+    KRY_FOR_GROUPS(T, n, chunk) {
+        Grp<T> gx = ld<T, VEC>(x, j, cnt), gr = ld<T, VEC>(r, j, cnt);
+        const Grp<T> gp = ld<T, VEC>(p, j, cnt), gq = ld<T, VEC>(q, j, cnt);
+#pragma unroll
+        for (int k = 0; k < Grp<T>::V; k++) {
+            gx.e[k] = gx.e[k] + ta * gp.e[k];
+            gr.e[k] = gr.e[k] - ta * gq.e[k];
+            if (k < cnt) rr += (double)gr.e[k] * (double)gr.e[k];
+        }
+        st<T, VEC>(x, j, cnt, gx);
+        st<T, VEC>(r, j, cnt, gr);
+        if constexpr (COPY) st_copy32<VEC>(copy32, j, cnt, gr);
+    }
+    put_partial(blk, kKryPartRR, block_sum(rr, lds));
+}
+
 // ---------------------------------------------------------------- GMRES
 //
 // Restarted flexible GMRES (rsp_gmres_*) and rsp_orthogonalize. Column j of a
@@ -740,7 +878,8 @@ hipError_t launch(KryOp op, const KryArgs &a, hipStream_t s) {
     const KryGrid kg = kry_grid(a.n);
     const dim3 grid(kg.grid), block(kKryThreads);
     const long long n = a.n, ch = kg.chunk;
-    const T *b = (const T *)a.b, *c = (const T *)a.c, *phat = (const T *)a.phat, *shat = (const T *)a.shat;
+    const T *b = (const T *)a.b, *c = (const T *)a.c, *phat = (const T *)a.phat, *shat = (const T *)a.shat,
+            *z = (const T *)a.z;
     T *x = (T *)a.x, *r = (T *)a.r, *rhat = (T *)a.rhat, *p = (T *)a.p, *v = (T *)a.v, *sv = (T *)a.s,
       *t = (T *)a.t;
     float *c32 = (float *)a.copy32;
@@ -782,6 +921,26 @@ hipError_t launch(KryOp op, const KryArgs &a, hipStream_t s) {
             break;
         case kKryDot:
             KRY_LAUNCH(aligned16({b, c}), (kry_dot<T, true>), (kry_dot<T, false>), n, ch, a.blk, b, c);
+            break;
+        case kKryCgInit:
+            KRY_LAUNCH(aligned16({b, v, r, c32}), (cg_init<T, true, COPY>), (cg_init<T, false, COPY>), n, ch, a.blk,
+                       b, (const T *)v, r, c32);
+            break;
+        case kKryCgDotRZ:
+            KRY_LAUNCH(aligned16({r, z}), (cg_dot<T, true, kKryPartRZ>), (cg_dot<T, false, kKryPartRZ>), n, ch,
+                       a.blk, (const T *)r, z);
+            break;
+        case kKryCgPUpdate:
+            KRY_LAUNCH(aligned16({z, p}), (cg_p_update<T, true>), (cg_p_update<T, false>), n, ch, a.blk, a.it,
+                       (int)(z == r ? kKryPartRR : kKryPartRZ), z, p);
+            break;
+        case kKryCgDotPQ:
+            KRY_LAUNCH(aligned16({p, v}), (cg_dot<T, true, kKryPartPQ>), (cg_dot<T, false, kKryPartPQ>), n, ch,
+                       a.blk, (const T *)p, (const T *)v);
+            break;
+        case kKryCgXUpdate:
+            KRY_LAUNCH(aligned16({x, r, p, v, c32}), (cg_x_update<T, true, COPY>), (cg_x_update<T, false, COPY>), n,
+                       ch, a.blk, a.it, x, r, (const T *)p, (const T *)v, c32);
             break;
         default:
             return hipErrorInvalidValue;

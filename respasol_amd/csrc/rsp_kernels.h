@@ -497,7 +497,7 @@ struct TrsvArgs {
 
 
 // Krylov vector kernels (krylov.hip): the solver's own side of a BiCGStab
-// iteration (rsp_bicgstab_*), of GMRES (rsp_gmres_*, below) and rsp_dot. Every kernel runs kry_grid(n)
+// iteration (rsp_bicgstab_*), of CG (rsp_cg_*), of GMRES (rsp_gmres_*, below) and rsp_dot. Every kernel runs kry_grid(n)
 // workgroups of kKryThreads threads; workgroup g owns the contiguous elements
 // [g * chunk, min(n, (g + 1) * chunk)), so the grid and every summation order
 // are functions of n alone. A dot leaves one fp64 partial per workgroup
@@ -529,8 +529,17 @@ enum {
     kKryFlagIt = 5, // the iteration that set it
     kKryScalars = 16
 };
-enum { kKryPartRR = 0, kKryPartBB, kKryPartRhR, kKryPartRhV, kKryPartTS, kKryPartTT, kKryDots };
-enum { kKryBreakRho = 1, kKryBreakOmega = 2, kKryBreakRhV = 3, kKryBreakTT = 4 };
+enum {
+    kKryPartRR = 0, kKryPartBB, kKryPartRhR, kKryPartRhV, kKryPartTS, kKryPartTT,
+    kKryPartRZ,  // CG: (r,z), with M only (M = I: z is r and kKryPartRR is read)
+    kKryPartPQ,  // CG: (p,q), q = A p
+    kKryDots
+};
+enum {
+    kKryBreakRho = 1, kKryBreakOmega = 2, kKryBreakRhV = 3, kKryBreakTT = 4,
+    kKryBreakCgRZ = 5,  // CG: (r,z) <= 0 or not finite: M is not positive definite (or r == 0)
+    kKryBreakCgPQ = 6   // CG: (p,q) <= 0 or not finite: A is not positive definite
+};
 constexpr size_t kKryBlockDoubles = kKryScalars + (size_t)kKryDots * kKryMaxGrid;
 enum KryOp {
     kKryInit,     // r = b - v (v = A x0), rhat = r; partials (b,b), (r,r), (rhat,r); scalars reset
@@ -541,7 +550,13 @@ enum KryOp {
     kKryXUpdate,  // omega = (t,s)/(t,t); x += alpha phat + omega shat; r = s - omega t; (rhat,r), (r,r)
     kKryWiden,    // dst (fp64) = src (fp32): the preconditioner's result for the fp64 SpMV
     kKryZero,     // x = 0
-    kKryDot       // partials[kKryPartRR] of (x, y): rsp_dot
+    kKryDot,      // partials[kKryPartRR] of (x, y): rsp_dot
+    // preconditioned CG (rsp_cg_*): rho in the parity slots as above, alpha in kKryAlpha
+    kKryCgInit,     // r = b - v (v = A x0)  [+ fp32 copy]; partials (b,b), (r,r); scalars reset
+    kKryCgDotRZ,    // (r,z), z = M^-1 r; not launched when M = I
+    kKryCgPUpdate,  // rho' from (r,z) (z == r: from (r,r)); beta = rho'/rho; p = z + beta p
+    kKryCgDotPQ,    // (p,v), v = A p
+    kKryCgXUpdate   // alpha = rho'/(p,v); x += alpha p; r -= alpha v  [+ fp32 copy]; (r,r)
 };
 // type codes: the iteration type, and whether p / s get an fp32 copy
 enum { kKryF64 = 0, kKryF32 = 1, kKryF64Copy32 = 2 };
@@ -553,7 +568,8 @@ struct KryArgs {
     const void *c;    // kKryDot: y
     void *x, *r, *rhat, *p, *v, *s, *t;
     const void *phat, *shat;
-    void *copy32;     // kKryF64Copy32: the fp32 copy of p / s; kKryWiden: dst (fp64)
+    void *copy32;     // kKryF64Copy32: the fp32 copy of p / s (CG: of r); kKryWiden: dst (fp64)
+    const void *z;    // CG: M^-1 r (M = I: r itself); v is CG's q = A p
 };
 // kry_combine_host: the device's sum of g partials, restated: thread t adds
 // part[t], part[t + 256], ... in that order, then the 64-lane down-tree

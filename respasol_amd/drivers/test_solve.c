@@ -1,20 +1,23 @@
 /*
- * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) driver (built as
- * `test_solve`).
+ * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) / CG driver (built
+ * as `test_solve`).
  * No GPU counterpart in the reference; shaped like its direct-solver drivers
  * (Pardiso/test_pardiso.c): b = 1 (:107), solve, relative residual ||b - A x||
  * / ||b|| recomputed on the host (:258-274).
  *
  *   test_solve <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32]
  *              [--precond=fp64|fp32|none] [--ftz] [--rtol=R] [--maxit=N]
- *              [--full-symmetric] [--dump=FILE] [--method=bicgstab|gmres]
+ *              [--full-symmetric] [--dump=FILE] [--method=bicgstab|gmres|cg]
  *              [--restart=M]
  *
  * Flow: load as test_ilu0 does (outputbase 0); iteration values in --prec;
  * b = 1, x0 = 0; [timed "Symbolic"] ILU analysis; [timed "Numeric"]
  * factorisation of a copy of the values in the --precond type (default: the
  * --prec type; must not be wider); [timed "Solve"] rsp_bicgstab_solve, or with --method=gmres
- * rsp_gmres_solve of restart length --restart (default 30); the six-line
+ * rsp_gmres_solve of restart length --restart (default 30), or with
+ * --method=cg rsp_cg_solve (A must be symmetric positive definite; a file
+ * whose banner says symmetric is then loaded with both triangles, as under
+ * --full-symmetric, and a general file is taken as it is); the six-line
  * report. Symbolic is wall-clock, Numeric and Solve are event pairs
  * on the stream. The residual line is the TRUE residual, in fp64 on the host
  * (rsp_host_spmv_f64 on the file's fp64 values), not the recurrence's.
@@ -64,10 +67,12 @@ int main(int argc, char **argv) {
                 "-- Usage --\n"
                 "  %s <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32] [--precond=fp64|fp32|none]\n"
                 "     [--ftz] [--rtol=R] [--maxit=N] [--full-symmetric] [--dump=FILE]\n"
-                "     [--method=bicgstab|gmres] [--restart=M]\n"
+                "     [--method=bicgstab|gmres|cg] [--restart=M]\n"
                 "  solves A x = 1 from x0 = 0 by ILU(0)-preconditioned BiCGStab.\n"
                 "  --method=gmres: by restarted flexible GMRES(M) instead (--restart, default 30).\n"
-                "  A symmetric file loads as its lower triangle unless --full-symmetric is given.\n",
+                "  --method=cg: by preconditioned conjugate gradients (A symmetric positive definite).\n"
+                "  A symmetric file loads as its lower triangle unless --full-symmetric is given\n"
+                "  or --method=cg, which needs both triangles, is.\n",
                 argv[0]);
         return 2;
     }
@@ -79,14 +84,15 @@ int main(int argc, char **argv) {
     const char *method = drv_flag(argc, argv, 2, "method");
     const char *restart_s = drv_flag(argc, argv, 2, "restart");
     const int gmres = method && strcmp(method, "gmres") == 0;
+    const int cg = method && strcmp(method, "cg") == 0;
     const int restart = restart_s && *restart_s ? atoi(restart_s) : 30;
-    if (method && *method && !gmres && strcmp(method, "bicgstab") != 0) {
-        fprintf(stderr, "Error: --method is bicgstab or gmres\n");
+    if (method && *method && !gmres && !cg && strcmp(method, "bicgstab") != 0) {
+        fprintf(stderr, "Error: --method is bicgstab, gmres or cg\n");
         return 2;
     }
     const int fp32 = prec && strcmp(prec, "fp32") == 0;
     const int ftz = drv_flag(argc, argv, 2, "ftz") != NULL;
-    const int fullsym = drv_flag(argc, argv, 2, "full-symmetric") != NULL;
+    const int fullsym = cg || drv_flag(argc, argv, 2, "full-symmetric") != NULL;
     const int use_m = !(precond && strcmp(precond, "none") == 0);
     const int m32 = precond && *precond && use_m ? strcmp(precond, "fp32") == 0 : fp32;
     const double rtol = rtol_s && *rtol_s ? atof(rtol_s) : (fp32 ? 1e-4 : 1e-10);
@@ -166,8 +172,11 @@ int main(int argc, char **argv) {
 
     rsp_bicgstab_t solver = NULL;
     rsp_gmres_t gsolver = NULL;
+    rsp_cg_t csolver = NULL;
     if (gmres)
         RSP_OR_FAIL(rsp_gmres_create(handle, mat, info, mt, d_m, restart, &gsolver));
+    else if (cg)
+        RSP_OR_FAIL(rsp_cg_create(handle, mat, info, mt, d_m, &csolver));
     else
         RSP_OR_FAIL(rsp_bicgstab_create(handle, mat, info, mt, d_m, &solver));
     int iters = 0;
@@ -176,6 +185,8 @@ int main(int argc, char **argv) {
     HIP_OR_FAIL(hipEventRecord(start, NULL));
     if (gmres)
         RSP_OR_FAIL(rsp_gmres_solve(handle, gsolver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
+    else if (cg)
+        RSP_OR_FAIL(rsp_cg_solve(handle, csolver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
     else
         RSP_OR_FAIL(rsp_bicgstab_solve(handle, solver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
     HIP_OR_FAIL(hipEventRecord(stop, NULL));
@@ -210,6 +221,8 @@ int main(int argc, char **argv) {
     hipEventDestroy(stop);
     if (gmres)
         rsp_gmres_destroy(gsolver);
+    else if (cg)
+        rsp_cg_destroy(csolver);
     else
         rsp_bicgstab_destroy(solver);
     if (info) rsp_destroy_ilu0_info(info);

@@ -25,6 +25,8 @@ Mapping to the reference's cuSPARSE usage:
   BiCGStab               the loop those calls are normally used in: ILU(0)-
                          preconditioned BiCGStab (rsp_bicgstab_*; no single
                          cuSPARSE call)
+  CG                     ILU(0)-preconditioned conjugate gradients for a
+                         symmetric positive definite A (rsp_cg_*)
   GMRES                  restarted flexible GMRES(m) on the same operators
                          (rsp_gmres_*)
   dot                    cublasDdot on the solver's reduction (rsp_dot)
@@ -388,7 +390,7 @@ class Ilu0:
 
 
 class SolveResult:
-    """What BiCGStab.solve and GMRES.solve return: x (the solution tensor), iters, relres
+    """What BiCGStab.solve, CG.solve and GMRES.solve return: x (the solution tensor), iters, relres
     (recurrence ||r|| / ||b|| at the last check), reason (_lib.SOLVE_*) and
     history (relres after each checked iteration)."""
 
@@ -450,6 +452,59 @@ class BiCGStab:
     def close(self) -> None:
         if self._s:
             rsp.rsp_bicgstab_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CG:
+    """Preconditioned conjugate gradients on a symmetric positive definite A
+    (rsp_cg_*); the arguments are BiCGStab's. A's symmetry is not verified: an
+    A or M that is not positive definite ends in BREAKDOWN. Memory: 4 vectors
+    of A's dtype (3 without `ilu`)."""
+
+    CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
+
+    def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
+                 factor: torch.Tensor | None = None):
+        if ilu is not None and factor is None:
+            raise ValueError("an ILU(0) preconditioner needs its factored values")
+        if factor is not None and factor.dtype not in _DT:
+            raise TypeError("factor must be float64 or float32")
+        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.dtype = A.dtype
+        self._s = C.c_void_p()
+        check(rsp.rsp_cg_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
+                                _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
+                                _ptr(factor) if ilu is not None else None, C.byref(self._s)),
+              "rsp_cg_create")
+
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, rtol: float = 1e-10,
+              max_iters: int = 1000, check_every: int = 1) -> SolveResult:
+        """Solve A x = b from x0 (default 0); x0 is not modified."""
+        if b.dtype != self.dtype or b.numel() != self.A.m:
+            raise ValueError("b has the wrong dtype or length")
+        if x0 is not None and (x0.dtype != self.dtype or x0.numel() != self.A.m):
+            raise ValueError("x0 has the wrong dtype or length")
+        with torch.cuda.stream(self.handle.stream):
+            x = torch.zeros_like(b) if x0 is None else x0.clone()
+        iters, reason, rel = C.c_int(), C.c_int(), C.c_double()
+        check(rsp.rsp_cg_solve(self.handle.ptr, self._s, _ptr(b), _ptr(x), float(rtol), int(max_iters),
+                               int(check_every), C.byref(iters), C.byref(rel), C.byref(reason)),
+              "rsp_cg_solve")
+        count = C.c_int()
+        check(rsp.rsp_cg_history(self._s, 0, None, C.byref(count)), "rsp_cg_history")
+        hist = (C.c_double * max(count.value, 1))()
+        check(rsp.rsp_cg_history(self._s, count.value, hist, C.byref(count)), "rsp_cg_history")
+        return SolveResult(x, iters.value, rel.value, reason.value, list(hist[:count.value]))
+
+    def close(self) -> None:
+        if self._s:
+            rsp.rsp_cg_destroy(self._s)
             self._s = C.c_void_p()
 
     def __del__(self):  # pragma: no cover
@@ -598,5 +653,5 @@ def csr_transpose_host(rowptr, colidx, n_cols: int):
     return t_rp, t_ci, perm
 
 
-__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "GMRES", "SolveResult", "dot", "orthogonalize", "upload_csr",
+__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "CG", "GMRES", "SolveResult", "dot", "orthogonalize", "upload_csr",
            "gather", "scatter", "csr2csc", "csr_transpose_host", "RspError"]

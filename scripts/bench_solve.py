@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""ILU(0)-preconditioned BiCGStab or GMRES(m) on the moderate surrogates: does a
-narrower preconditioner reach the same residual in less time?
+"""ILU(0)-preconditioned BiCGStab, GMRES(m) or CG on the moderate surrogates: does
+a narrower preconditioner reach the same residual in less time?
 
     python scripts/bench_solve.py [--names A,B] [--scale S] [--rtol R] [--maxit N]
-                                  [--method bicgstab|gmres] [--restart M]
-                                  [--out FILE.jsonl]
+                                  [--method bicgstab|gmres|cg] [--restart M]
+                                  [--both-triangles] [--out FILE.jsonl]
 
 Per matrix (b = 1, x0 = 0, fp64 iteration) and per configuration
     fp64      fp64 ILU(0) factor and solves
@@ -25,6 +25,17 @@ adds is its four kernels per iteration (five with a narrower preconditioner),
 the cycle ends and the read-backs; BiCGStab's applies = 2 iterations. A matrix that ends in MAX_ITERS or BREAKDOWN is a result, not a
 failure. A symmetric surrogate is its stored lower triangle (as everywhere in
 this project), so its ILU(0) is exact and one iteration solves it.
+
+--method cg (preconditioned conjugate gradients, rsp_cg_*) needs the whole
+symmetric matrix: it runs on the surrogates whose surrogate_info(...)
+["symmetric"] is set, each expanded on the host to both triangles (A + A^T -
+diag, rows sorted), and skips the others with a note. An iteration is one SpMV
+and one apply: applies = iterations, own_ms = solve_ms - iterations * (spmv_ms
++ apply_ms), what the solver adds being its four kernels per iteration (five
+with a narrower preconditioner) and the read-backs. A surrogate expanded this
+way is not guaranteed positive definite: BREAKDOWN is then the result.
+--both-triangles gives BiCGStab and GMRES the same expanded matrices (and the
+same skipping), for a comparison on equal systems.
 """
 from __future__ import annotations
 
@@ -41,7 +52,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from respasol_amd import _lib, csr  # noqa: E402
-from respasol_amd.sparse import GMRES, BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
+from respasol_amd.sparse import CG, GMRES, BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
 
 CONFIGS = (("fp64", torch.float64, False), ("fp32", torch.float32, False), ("fp32ftz", torch.float32, True))
 
@@ -67,10 +78,27 @@ def true_relres(A, x):
     return float(np.linalg.norm(1.0 - ax) / np.sqrt(A.m))
 
 
+def both_triangles(A):
+    """A + A^T - diag of a stored lower triangle, rows sorted (host)."""
+    rows = np.repeat(np.arange(A.m, dtype=np.int64), np.diff(A.rowptr))
+    cols = A.colidx.astype(np.int64)
+    off = rows != cols
+    r = np.concatenate([rows, cols[off]])
+    c = np.concatenate([cols, rows[off]])
+    v = np.concatenate([A.values, A.values[off]])
+    order = np.lexsort((c, r))
+    r, c, v = r[order], c[order], v[order]
+    if np.any((r[1:] == r[:-1]) & (c[1:] == c[:-1])):
+        raise ValueError("the stored part holds both (i, j) and (j, i)")
+    rp = np.zeros(A.m + 1, np.int32)
+    rp[1:] = np.cumsum(np.bincount(r, minlength=A.m))
+    return csr.CsrMatrix(1, A.m, A.n, len(c), rp, c.astype(np.int32), np.ascontiguousarray(v), 0)
+
+
 def run_one(name, A, cfg, rtol, maxit, method="bicgstab", restart=30):
     label, pdt, ftz = cfg
     rec = {"matrix": name, "config": label, "method": method, "n": A.m, "nnz": A.nnz_stored}
-    per_iter = 1 if method == "gmres" else 2  # SpMVs (and applies) per iteration
+    per_iter = 2 if method == "bicgstab" else 1  # SpMVs (and applies) per iteration
     h = Handle(ftz=ftz)
     rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
     mat = SpMat(h, rp, ci, va, A.n)
@@ -82,7 +110,7 @@ def run_one(name, A, cfg, rtol, maxit, method="bicgstab", restart=30):
         ilu.factor(fac)
         try:
             solver = (GMRES(h, mat, ilu, fac, restart=restart) if method == "gmres"
-                      else BiCGStab(h, mat, ilu, fac))
+                      else CG(h, mat, ilu, fac) if method == "cg" else BiCGStab(h, mat, ilu, fac))
         except RspError as e:
             rec["error"] = str(e)
             return rec
@@ -122,8 +150,10 @@ def main(argv=None):
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--rtol", type=float, default=1e-10)
     ap.add_argument("--maxit", type=int, default=200)
-    ap.add_argument("--method", choices=("bicgstab", "gmres"), default="bicgstab")
+    ap.add_argument("--method", choices=("bicgstab", "gmres", "cg"), default="bicgstab")
     ap.add_argument("--restart", type=int, default=30, help="GMRES restart length")
+    ap.add_argument("--both-triangles", action="store_true",
+                    help="symmetric surrogates only, expanded to both triangles (implied by --method cg)")
     ap.add_argument("--configs", default="", help="comma-separated subset of fp64,fp32,fp32ftz")
     ap.add_argument("--out", default="", help="also append the records to this file")
     args = ap.parse_args(argv)
@@ -133,6 +163,11 @@ def main(argv=None):
     out = open(args.out, "a") if args.out else None
     for name in names:
         A = csr.surrogate(name, args.scale)
+        if args.method == "cg" or args.both_triangles:
+            if not csr.surrogate_info(name)["symmetric"]:
+                print(f"# {name}: not symmetric, skipped", file=sys.stderr, flush=True)
+                continue
+            A = both_triangles(A)
         for cfg in CONFIGS:
             if args.configs and cfg[0] not in args.configs.split(","):
                 continue
