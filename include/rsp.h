@@ -626,6 +626,29 @@ rsp_status_t rsp_ilu0_plan_facts_host(int n, const int *row_offsets, const int *
 rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
                                 rsp_datatype_t compute_type, int64_t *tiles, int64_t *entries_16bit,
                                 int64_t *entries_staged);
+/* Tests (no device needed): the same schedule tile by tile. The plan is made
+ * for the given planner options (spread: resident workgroup slots a small plan
+ * is spread over, 0 none; local_cols: rsp_spmat_set_local_cols, -1 none;
+ * row_align >= 1: rows a packed tile's end is aligned to; use_c16 / use_stage:
+ * 0 switches the 16-bit offsets / the staged tiles off) and the environment's
+ * plan-time knobs, checked as rsp_spmv_plan_host checks it (INTERNAL_ERROR if
+ * the check fails), and the first max_tiles tiles are written in plan order as
+ * RSP_SPMV_TILE_FACTS integers each:
+ *   +0 r0, the first row; +1 r1 as stored: the row after the last, INT_MIN for
+ *   a whole long row, -(slot + 1) for a chunk of a longer one; +2 / +3 k0 / k1,
+ *   the entries; +4 kind: 0 int32 col_ind, 1 16-bit offsets from a base, 2
+ *   staged by runs, 3 staged by a column list; +5 the column base (kind 1) or
+ *   the smallest column (kinds 2, 3), 0 for kind 0; +6 U, the distinct columns
+ *   of a staged tile; +7 R, the contiguous runs they form (kind 2: the
+ *   descriptors before the sentinel); +8 1 with a packed record; +9 1 if the
+ *   record holds the row offsets.
+ * counts[0] tiles (all of them, also past max_tiles); [1] interior tiles of a
+ * split schedule; [2] rows cut into chunks; [3] their partial slots. */
+#define RSP_SPMV_TILE_FACTS 10
+rsp_status_t rsp_spmv_plan_tiles_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
+                                      rsp_datatype_t compute_type, int64_t spread, int64_t local_cols, int row_align,
+                                      int use_c16, int use_stage, int64_t *facts, int64_t max_tiles,
+                                      int64_t counts[4]);
 /* Profiling (no cuSPARSE counterpart; scripts/bench_spmv_t.py): the
  * permutation pass of rsp_spmv(op = TRANSPOSE) alone, on the handle's stream:
  * the current values of `mat` into its transposed side, no product.

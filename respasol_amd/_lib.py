@@ -147,6 +147,8 @@ RSP_PROTOS = {
     "rsp_ilu0_plan_facts_host": (i32, [i32, vp, vp, vp, i32]),
     "rsp_spmv_plan_host": (i32, [i32, vp, vp, C.c_int64, i32, vp, vp, vp]),
     "rsp_spmv_plan_stats": (i32, [i32, vp, vp, C.c_int64, i32, vp]),
+    "rsp_spmv_plan_tiles_host": (i32, [i32, vp, vp, C.c_int64, i32, C.c_int64, C.c_int64, i32, i32, i32, vp,
+                                       C.c_int64, vp]),
     "rsp_ilu0_plan_digest": (i32, [vp, vp]),
     "rsp_csr2csc": (i32, [vp, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]),
     "rsp_csr_transpose_host": (i32, [i64, i64, vp, vp, vp, vp, vp]),

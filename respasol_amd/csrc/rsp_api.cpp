@@ -875,6 +875,35 @@ rsp_status_t rsp_spmv_plan_host(int m, const int *row_offsets, const int *col_in
     });
 }
 
+rsp_status_t rsp_spmv_plan_tiles_host(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
+                                      rsp_datatype_t compute_type, int64_t spread, int64_t local_cols, int row_align,
+                                      int use_c16, int use_stage, int64_t *facts, int64_t max_tiles,
+                                      int64_t counts[4]) {
+    return guarded([&] {
+        if (m < 0 || (m > 0 && (!row_offsets || !col_ind)) || !counts || max_tiles < 0 || (max_tiles > 0 && !facts) ||
+            row_align < 1)
+            return RSP_STATUS_INVALID_VALUE;
+        if (compute_type != RSP_R_64F && compute_type != RSP_R_32F) return RSP_STATUS_NOT_SUPPORTED;
+        PlanOptions o = rsp_plan::plan_options(compute_type);
+        o.spread = spread;
+        o.local_cols = local_cols;
+        o.row_align = row_align;
+        o.use_c16 = use_c16 != 0;
+        o.use_stage = use_stage != 0;
+        TilePlan p;
+        rsp_plan::make_tile_plan(row_offsets, col_ind, m, nnz, o, p);
+        if (!rsp_plan::plan_verify(row_offsets, col_ind, m, o, p)) return RSP_STATUS_INTERNAL_ERROR;
+        const int64_t nt = (int64_t)p.blocks.size();
+        for (int64_t t = 0; t < std::min(nt, max_tiles); t++)
+            rsp_plan::tile_facts(p, (size_t)t, facts + t * RSP_SPMV_TILE_FACTS);
+        counts[0] = nt;
+        counts[1] = p.nint;
+        counts[2] = (int64_t)p.longrows.size();
+        counts[3] = p.nslots;
+        return RSP_STATUS_SUCCESS;
+    });
+}
+
 rsp_status_t rsp_spmv_plan_stats(int m, const int *row_offsets, const int *col_ind, int64_t nnz,
                                  rsp_datatype_t compute_type, int64_t stats[8]) {
     return guarded([&] {

@@ -255,6 +255,14 @@ __device__ __forceinline__ void stream_products_staged(const unsigned short *__r
         for (int k = 0; k < SMAX; ++k)
             if (k * NTH < U) xs[k] = xload(rd.x + lsl[k]);
     } else {  // runs mode: the run table at the end of the LDS image, a search per slot
+        // The table (nr <= kStageRuns descriptors and the sentinel, 8 B each)
+        // ends with the image and starts at element kSlots - 255 = 1793 (fp64)
+        // or kSlots - 2 * 255 = 3586 (fp32) at the lowest; the x staged below
+        // fills elements [0, U), U <= kStageSlots = 1536 / 2048: they never meet.
+        static_assert(SpmvTile<T>::kStageSlots * sizeof(T) + (rsp::kStageRuns + 1) * sizeof(int2) <=
+                          SpmvTile<T>::kSlots * sizeof(T),
+                      "the run table lies past the staged x in the LDS image");
+        static_assert(rsp::kStageRuns + 1 <= NTH, "one thread per run descriptor and the sentinel");
         int2 *tab = reinterpret_cast<int2 *>(lds + SpmvTile<T>::kSlots) - (nr + 1);
         if (tid <= nr) tab[tid] = rd;
         lds_barrier();

@@ -400,6 +400,34 @@ void plan_stats(const TilePlan &p, rsp_datatype_t type, int64_t out[8]) {
     out[7] = rows16;
 }
 
+void tile_facts(const TilePlan &p, size_t t, int64_t out[RSP_SPMV_TILE_FACTS]) {
+    const SpmvBlock &b = p.blocks[t];
+    const int cb = p.cbase[t], po = p.poff[t];
+    int64_t kind = 0, base = 0, U = 0, R = 0;
+    if (staged(cb)) {
+        const StageCode sc = stage_decode(cb);
+        const int *r = p.runs.data() + 2 * (size_t)sc.off;
+        base = r[0];
+        if (sc.list()) {  // R: the runs its listed columns form
+            const uint16_t *ofs = reinterpret_cast<const uint16_t *>(r + 2);
+            kind = 3;
+            U = r[1];
+            R = 1;
+            for (int u = 1; u < U; u++) R += ofs[u] != ofs[u - 1] + 1;
+        } else {
+            kind = 2;
+            U = r[2 * sc.nr + 1];
+            R = sc.nr;
+        }
+    } else if (cb != kCbaseInt32) {
+        kind = 1;
+        base = cb;
+    }
+    const int64_t f[RSP_SPMV_TILE_FACTS] = {b.r0, b.r1, b.k0, b.k1, kind, base, U, R, po != kNoPack,
+                                            po != kNoPack && pack_decode(po).rows};
+    std::copy(f, f + RSP_SPMV_TILE_FACTS, out);
+}
+
 namespace {
 
 // The split schedule as `o` asks for it: tiles [0, nint) are interior, tile
@@ -488,19 +516,24 @@ bool plan_verify(const int *rp, const int *ci, int m, const PlanOptions &o, cons
                     (j < nr && r[2 * j] <= r[2 * j - 2] + (r[2 * j + 1] - r[2 * j - 1]) - 1))
                     return false;
         }
+        // a staged tile loads x for every slot below U: each is some entry's
+        // (a U that is too large would read a column no entry names)
+        std::vector<char> used(staged(cb) ? (size_t)std::max(U, 0) : 0, 0);
         for (int k = b.k0; k < b.k1; k++) {
             int col;
             if (cb >= 0) {
                 col = cb + p.c16[(size_t)k];
             } else {
                 const int u = slot_of(k);
-                if (u >= U) return false;
+                if (u >= U || (rec && p.c16[(size_t)k] != u)) return false;  // (the record repeats the 16-bit slots)
+                used[(size_t)u] = 1;
                 int j = 0;
                 while (!ofs && j + 1 < nr && r[2 * (j + 1) + 1] <= u) j++;
                 col = ofs ? r[0] + ofs[u] : r[2 * j] + (u - r[2 * j + 1]);
             }
             if (col != ci[k]) return false;
         }
+        if (std::find(used.begin(), used.end(), 0) != used.end()) return false;
     }
     return npk == p.tiles_packed && epk == p.nnz_packed && verify_split(ci, o, p);
 }

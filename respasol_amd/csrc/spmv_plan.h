@@ -2,8 +2,8 @@
 // header): tiles, long rows, per-tile column codes, 16-bit column offsets,
 // staged tiles' runs and packed records, and the layout of all that in the
 // matrix's device memory. Pure host C++ (no HIP calls): rsp_api.cpp downloads
-// the pattern, calls make_tile_plan and uploads the result; rsp_spmv_plan_host
-// / rsp_spmv_plan_stats run it on host arrays; drivers/spmv_plan_check.cpp
+// the pattern, calls make_tile_plan and uploads the result; rsp_spmv_plan_host,
+// rsp_spmv_plan_tiles_host and rsp_spmv_plan_stats run it on host arrays; drivers/spmv_plan_check.cpp
 // runs it under the sanitizers (make tsan-plan / asan-plan).
 #ifndef RSP_SPMV_PLAN_H
 #define RSP_SPMV_PLAN_H
@@ -113,14 +113,19 @@ void make_tile_plan(const int *rp, const int *ci, int m, int64_t nnz_bound, cons
 
 // Every 16-bit / staged column of `p` decoded back and compared with the
 // pattern; a packed tile's slots are read from its record's fields, whose
-// padding must be 0, and its packed row offsets are compared with the row
-// offsets; the split schedule and the switched-off codes as `o` says. `o`: the
+// padding must be 0 and whose slots must be those of the 16-bit array, and its
+// packed row offsets are compared with the row offsets; every slot of a staged
+// tile is some entry's; the split schedule and the switched-off codes as `o` says. `o`: the
 // options `p` was made with. false: the plan is wrong.
 bool plan_verify(const int *rp, const int *ci, int m, const PlanOptions &o, const TilePlan &p);
 
 // rsp_spmv_plan_stats: what one call over the schedule reads besides the
 // values, x and y (see include/rsp.h for the rule).
 void plan_stats(const TilePlan &p, rsp_datatype_t type, int64_t out[8]);
+
+// rsp_spmv_plan_tiles_host: tile t of a verified plan as RSP_SPMV_TILE_FACTS
+// integers (include/rsp.h), read through stage_decode / pack_decode alone.
+void tile_facts(const TilePlan &p, size_t t, int64_t out[RSP_SPMV_TILE_FACTS]);
 
 // 64-bit digest (rsp_an::Fnv) of every array and scalar of the plan.
 uint64_t digest(const TilePlan &p);

@@ -248,6 +248,32 @@ def spmv_plan_stats(rowptr, colidx, fp32: bool = False, nnz: int | None = None) 
     return dict(zip(PLAN_STATS, (int(v) for v in out)))
 
 
+TILE_FACTS = ("r0", "r1", "k0", "k1", "kind", "base", "U", "R", "packed", "packed_rows")
+TILE_KINDS = ("int32", "gather16", "runs", "list")
+
+
+def spmv_plan_tiles(rowptr, colidx, fp32: bool = False, nnz: int | None = None, spread: int = 0,
+                    local_cols: int = -1, row_align: int = 1, use_c16: bool = True, use_stage: bool = True) -> dict:
+    """The verified schedule of a HOST pattern tile by tile
+    (rsp_spmv_plan_tiles_host; no device needed): {"tiles": [one dict of
+    TILE_FACTS per tile, "kind" as a TILE_KINDS name], "nint", "nlong",
+    "nslots"}. The plan-time knobs come from the environment."""
+    import numpy as np
+
+    rp = np.ascontiguousarray(rowptr, np.int32)
+    ci = np.ascontiguousarray(colidx, np.int32)
+    args = (len(rp) - 1, rp.ctypes.data, ci.ctypes.data, int(nnz if nnz is not None else len(ci)), 1 if fp32 else 0,
+            int(spread), int(local_cols), int(row_align), int(use_c16), int(use_stage))
+    counts = (C.c_int64 * 4)()
+    check(rsp.rsp_spmv_plan_tiles_host(*args, None, 0, counts), "rsp_spmv_plan_tiles_host")
+    facts = np.zeros((counts[0], len(TILE_FACTS)), np.int64)
+    check(rsp.rsp_spmv_plan_tiles_host(*args, facts.ctypes.data, facts.shape[0], counts), "rsp_spmv_plan_tiles_host")
+    tiles = [dict(zip(TILE_FACTS, (int(v) for v in row))) for row in facts]
+    for t in tiles:
+        t["kind"] = TILE_KINDS[t["kind"]]
+    return {"tiles": tiles, "nint": int(counts[1]), "nlong": int(counts[2]), "nslots": int(counts[3])}
+
+
 class SpmvBatch:
     """Several independent products y_j = alpha*A_j*x_j (+ beta*y_j) as one
     launch (rsp_spmv_batch_*): the same bits per matrix as SpMat.spmv /

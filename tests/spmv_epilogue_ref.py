@@ -269,6 +269,23 @@ def stencil_case(dtype, spec):
     return Case(A, rng.uniform(-1, 1, A.n).astype(dtype), rng.uniform(-1, 1, A.m).astype(dtype))
 
 
+def tile_lanes(nrows, nnz):
+    """Lanes per row of a tile of `nrows` rows and `nnz` entries (spmv.hip
+    reduce_tile_rows): doubled from 1 up to 8 while two groups of rows still
+    fit the 256 threads and every lane still sums 4 products of an average row."""
+    L = 1
+    while L < 8 and 2 * L * nrows <= 256 and 8 * L * nrows <= nnz:
+        L <<= 1
+    return L
+
+
+def heavy_rows_of_tile(lens, start, end):
+    """(L, the rows of [start, end) that tile hands to reduce_heavy_rows):
+    with L < 8, the rows of more than 32 L entries."""
+    L = tile_lanes(end - start, int(np.sum(lens[start:end])))
+    return L, [i for i in range(start, end) if L < 8 and lens[i] > 32 * L]
+
+
 def heavy_pass_rows(lens, cap, maxrows):
     """The rows that reduce_heavy_rows sums under the full-tile schedule
     (spmv_plan.cpp build_spmv_plan, spmv.hip reduce_tile_rows): consecutive rows
@@ -286,9 +303,5 @@ def heavy_pass_rows(lens, cap, maxrows):
                 break
             nnz += int(lens[r])
             r += 1
-        nrows, L = r - start, 1
-        while L < 8 and 2 * L * nrows <= 256 and 8 * L * nrows <= nnz:
-            L <<= 1
-        if L < 8:
-            out += [i for i in range(start, r) if lens[i] > 32 * L]
+        out += heavy_rows_of_tile(lens, start, r)[1]
     return np.array(out, np.int64)

@@ -141,3 +141,37 @@ def test_spmv_planner_clean_under_tsan_and_asan(plan_exes, name, scale):
         assert _clean(p)[0] and p.returncode == 0, p.stdout + p.stderr
         nolist = p.stdout.splitlines()[0].split()
         assert nolist[1:3] == ["f64", "default"] and int(nolist[8]) == 0
+
+
+PLAN_MUTANTS = {"c16", "cbase", "run-col", "run-slot", "sentinel", "slot-swap", "list-ofs", "list-u", "pack-pad",
+                "pack-field", "pack-row", "poff", "nint", "tile-swap"}
+
+
+@pytest.mark.parametrize("name,scale,absent64", [("atmosmodd", 0.05, {"c16", "cbase", "list-ofs", "list-u"}),
+                                                  ("cage13", 0.3, {"run-col", "run-slot", "sentinel", "slot-swap", "pack-pad",
+                                                                  "pack-field", "pack-row"}),
+                                                  ("dc1", 0.3, set())])
+def test_spmv_plan_verify_rejects_corrupted_plans(plan_exes, name, scale, absent64):
+    """spmv_plan_check --mutate: every test of the planner rests on
+    rsp_plan::plan_verify, so each of fourteen single corruptions of a valid
+    plan (an offset, a base, a run's column or slot, the sentinel, two slots, a
+    listed offset, a list's count, a record's padding, field or row offset, a
+    record on a tile too small for one, the interior count, two tiles) must
+    fail it; exit 5 names a corrupted plan that verified. dc1's fp64 plan has
+    every field, the stencil no gathered or list tile, cage13 at this scale
+    lists and gathered tiles only. Both builds, clean and
+    the same lines."""
+    env = dict(os.environ, OMP_NUM_THREADS="4", TSAN_OPTIONS="halt_on_error=1",
+               ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    outs = []
+    for exe in plan_exes:
+        p = subprocess.run([exe, "--mutate", name, str(scale)], env=env, capture_output=True, text=True, timeout=300)
+        ok, err = _clean(p)
+        assert ok and "ThreadSanitizer" not in err, err
+        assert p.returncode == 0, err
+        outs.append(p.stdout)
+    assert outs[0] == outs[1]
+    f64 = outs[0].splitlines()[0].split()
+    assert f64[1:3] == ["f64", "rejected"]
+    at = f64.index("absent")
+    assert set(f64[3:at]) == PLAN_MUTANTS - absent64 and set(f64[at + 1:]) == absent64

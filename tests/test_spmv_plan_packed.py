@@ -90,40 +90,77 @@ def stats(A, dt):
     return spmv_plan_stats(A.rowptr, A.colidx, fp32=dt == R32, nnz=int(max(A.nnz, A.nnz_stored)))
 
 
-def recount(A, dt, mode):
-    """The rule of include/rsp.h on the greedy tiles of a matrix without rows
-    longer than 256 entries, in numpy."""
+WHOLE_ROW = -2**31  # SpmvBlock::r1 of a whole long row (rsp_kernels.h kSpmvWholeRow)
+XELEM = {R64: 8, R32: 4}
+
+
+def greedy_cuts(rp, dt):
+    """(r0, r1, k0, k1) per tile of the full-tile schedule (spmv_plan.cpp
+    build_spmv_plan, row_align 1): a row of more than 256 entries is a tile of
+    its own (r1 = WHOLE_ROW) or, past cap entries, one tile per cap entries
+    (r1 = -(slot + 1)); the others are packed greedily."""
     g = GEO[dt]
-    rp, ci = np.asarray(A.rowptr, np.int64), np.asarray(A.colidx, np.int64)
-    assert np.diff(rp).max() <= 256
-    m, r = len(rp) - 1, 0
-    out = dict.fromkeys(("tiles", "packed_tiles", "packed_entries", "staged_tiles", "index_bytes",
-                         "packed_rowoff_bytes", "rowptr_bytes"), 0)
-    desc = 0
+    m, r, slot, cuts = len(rp) - 1, 0, 0, []
     while r < m:
+        ln = rp[r + 1] - rp[r]
+        if ln > 256:
+            if ln <= g["cap"]:
+                cuts.append((r, WHOLE_ROW, int(rp[r]), int(rp[r + 1])))
+            else:
+                for k in range(int(rp[r]), int(rp[r + 1]), g["cap"]):
+                    cuts.append((r, -(slot + 1), k, min(k + g["cap"], int(rp[r + 1]))))
+                    slot += 1
+            r += 1
+            continue
         s, nn = r, 0
         while r < m and r - s < g["maxrows"]:
             ln = rp[r + 1] - rp[r]
-            if r > s and nn + ln > g["cap"]:
+            if ln > 256 or (r > s and nn + ln > g["cap"]):
                 break
             nn += ln
             r += 1
-        cols = np.unique(ci[rp[s]:rp[r]])
-        U, R = len(cols), 1 + int(np.count_nonzero(np.diff(cols) != 1))
-        assert cols[-1] - cols[0] <= 65535
-        staged = U <= g["ucap"] and R <= STAGE_RUNS and 100 * U <= 80 * nn
-        assert staged or not (dt == R64 and U <= g["ucap"] and R > STAGE_RUNS), "list tile: not recounted here"
+        cuts.append((s, r, int(rp[s]), int(rp[r])))
+    return cuts
+
+
+def recount(A, dt, mode, pct=80, stage_list=True, cuts=None, use_c16=True, use_stage=True, tiles_out=None):
+    """The rule of include/rsp.h in numpy, tile by tile: on the greedy tiles
+    of the matrix, or on the tiles `cuts` names ((r0, r1, k0, k1) each, for
+    schedules the planner re-packed). tiles_out (a list) receives every tile
+    as a dict of respasol_amd.sparse.TILE_FACTS."""
+    g = GEO[dt]
+    rp, ci = np.asarray(A.rowptr, np.int64), np.asarray(A.colidx, np.int64)
+    out = dict.fromkeys(("tiles", "packed_tiles", "packed_entries", "staged_tiles", "index_bytes",
+                         "packed_rowoff_bytes", "rowptr_bytes"), 0)
+    desc = 0
+    for r0, r1, k0, k1 in (greedy_cuts(rp, dt) if cuts is None else cuts):
+        nn, nrows = k1 - k0, max(r1 - r0, 0)
+        kind, base, U, R = "int32", 0, 0, 0
+        if nn > 0 and use_c16:
+            cols = np.unique(ci[k0:k1])
+            if cols[-1] - cols[0] <= 65535:
+                u, runs = len(cols), 1 + int(np.count_nonzero(np.diff(cols) != 1))
+                kind, base = "gather16", int(cols[0])
+                if use_stage and r1 >= 0 and (cols[-1] + 1) * XELEM[dt] <= 0x7ffffffc and u <= g["ucap"]:
+                    if runs <= STAGE_RUNS and 100 * u <= pct * nn:
+                        kind, U, R = "runs", u, runs
+                    elif runs > STAGE_RUNS and dt == R64 and stage_list:
+                        kind, U, R = "list", u, runs
+        staged = kind in ("runs", "list")
         packed = staged and mode >= 1 and THREADS * ITER * g["vw"] * 12 // 8 < 2 * nn
         out["tiles"] += 1
         out["staged_tiles"] += staged
         out["packed_tiles"] += packed
         out["packed_entries"] += nn if packed else 0
-        out["index_bytes"] += 4 * THREADS * g["nw"] if packed else 2 * nn
-        desc += 8 * (R + 1) if staged else 0
+        out["index_bytes"] += 4 * THREADS * g["nw"] if packed else 4 * nn if kind == "int32" else 2 * nn
+        desc += 8 * (R + 1) if kind == "runs" else 8 + 2 * U if kind == "list" else 0
         if packed and mode >= 2:
-            out["packed_rowoff_bytes"] += 4 * ((r - s + 2) // 2)
+            out["packed_rowoff_bytes"] += 4 * ((nrows + 2) // 2)
         else:
-            out["rowptr_bytes"] += 4 * (r - s + 1)
+            out["rowptr_bytes"] += 4 * (nrows + 1)
+        if tiles_out is not None:
+            tiles_out.append(dict(r0=r0, r1=r1, k0=k0, k1=k1, kind=kind, base=base, U=U, R=R, packed=int(packed),
+                                  packed_rows=int(packed and mode >= 2)))
     out["schedule_bytes"] = 24 * out["tiles"] + out["index_bytes"] + desc + out["packed_rowoff_bytes"]
     return out
 
