@@ -459,6 +459,93 @@ rsp_status_t rsp_orthogonalize(rsp_handle_t handle, rsp_datatype_t value_type, i
  * pointer, a non-finite entry or a rotated diagonal that is 0. */
 rsp_status_t rsp_gmres_lsq_host(int k, int ldh, const double *H, double beta, double *y, double *est);
 
+/* --------------------- mixed-precision iterative refinement (rsp_refine_*)
+ *
+ * An fp64-accurate solution out of fp32 Krylov solves: the residual is formed
+ * in fp64, the correction equation is solved entirely in fp32 (fp32 matrix,
+ * fp32 vectors, fp32 ILU(0)) by one of the three solvers above, and the
+ * correction is added in fp64.
+ *
+ *   bn = ||b||                                    b = 0: x = 0, CONVERGED, 0 steps
+ *   k = 0, 1, ...
+ *      v = A x;  r = b - v;  rn = ||r||           (fp64; one rsp_spmv, one kernel, one read-back)
+ *      history[k] = rn / bn
+ *      rn or bn not finite:        BREAKDOWN      k = 0: x untouched;  k > 0: x = x_old
+ *      rn / bn <= rtol:            CONVERGED, steps = k
+ *      k > 0 and rn >= rn of k-1:  x = x_old, STAGNATED, steps = k - 1, relres = history[k-1]
+ *      k == max_steps:             MAX_ITERS, steps = k
+ *      rn = m * 2^e, 0.5 <= m < 1
+ *      r32_i = fp32(r_i * 2^-e);  d = 0           (one kernel; ||r32|| lies in [0.5, 1))
+ *      inner solve  A_low d = r32  from d = 0 to inner_rtol, inner_max_iters, check_every
+ *          inner BREAKDOWN before one iteration completed: BREAKDOWN, steps = k, x untouched
+ *      x_old = x;  x_i = x_i + 2^e * double(d_i)  (one kernel)
+ *
+ * A product with a power of two is exact, so r32 is r rounded once (to nearest
+ * even) and the update rounds once; the scaling lets the fp32 solve see
+ * residuals far below fp32's range, also under rsp_set_ftz(1) (e is kept
+ * within [-1022, 1022]). STAGNATED: a step that does not reduce ||r|| is
+ * undone and ends the solve — the floor of this A, A_low and inner solve is
+ * reached, and further steps would walk around it. Deterministic as
+ * rsp_bicgstab_*: equal inputs give bitwise equal x, counts and history.
+ * Memory: the inner solver's fp32 vectors, three fp64 and two fp32 vectors. */
+#define RSP_SOLVE_STAGNATED ((rsp_solve_reason_t)3) /* the fourth rsp_solve_reason_t; only rsp_refine_solve gives it */
+typedef enum { RSP_REFINE_BICGSTAB = 0, RSP_REFINE_CG = 1, RSP_REFINE_GMRES = 2 } rsp_refine_method_t;
+typedef struct rsp_refine *rsp_refine_t;
+/* A: square fp64 CSR (rows >= 1). A_low: an fp32 descriptor of the same size;
+ * the caller makes it over the same pattern arrays with the values narrowed by
+ * rsp_convert_scaled(exp2 = 0). info / d_factor_low: an analysed ILU(0) info of
+ * the pattern and its fp32 factor, or info = NULL for M = I. The inner solver
+ * is rsp_<method>_create(handle, A_low, info, RSP_R_32F, d_factor_low[,
+ * restart]); its statuses pass through, ZERO_PIVOT included. All vectors, the
+ * reduction block and its pinned mirror are allocated here. A, A_low, info and
+ * the factor must outlive the solver. INVALID_VALUE: a NULL argument (info may
+ * be NULL), A not fp64 or A_low not fp32, sizes that differ or are not square,
+ * a method outside the enum, for RSP_REFINE_GMRES a restart outside
+ * [1, RSP_GMRES_MAX_RESTART] (the other methods ignore restart). */
+rsp_status_t rsp_refine_create(rsp_handle_t handle, rsp_spmat_t A, rsp_spmat_t A_low, rsp_ilu0_info_t info,
+                               const void *d_factor_low, rsp_refine_method_t method, int restart,
+                               rsp_refine_t *s);
+/* The loop above; host-blocking. d_b, d_x: fp64, n elements; x is x0 on entry
+ * and the solution on return. *steps: accepted corrections; *inner_iters: the
+ * iterations of all inner solves, a rejected step's included; *relres: the
+ * last accepted history value, the true fp64 residual of the returned x over
+ * ||b||. max_steps = 0 computes the residual only. inner_max_iters = 0 makes
+ * every correction zero: STAGNATED with 0 steps. The inner solve's set-up
+ * product with d = 0 is not skipped: the inner solvers run as they are.
+ * INVALID_VALUE: a NULL pointer, max_steps < 0, inner_max_iters < 0,
+ * check_every < 1, a negative or NaN rtol or inner_rtol.
+ * EXECUTION_FAILED: an inner solve reported it (rsp_bicgstab_solve). */
+rsp_status_t rsp_refine_solve(rsp_handle_t handle, rsp_refine_t s, const void *d_b, void *d_x, double rtol,
+                              int max_steps, double inner_rtol, int inner_max_iters, int check_every,
+                              int *steps, int *inner_iters, double *relres, rsp_solve_reason_t *reason);
+/* The last solve step by step: relres[k] = history[k] above and inner_iters[k]
+ * = the iterations of the inner solve that produced x_k (0 for k = 0); a
+ * rejected step's entry is included, so *count = steps + 1 or steps + 2 (0
+ * after b = 0). The first min(cap, *count) entries of both are written.
+ * INVALID_VALUE: s or count NULL, cap < 0, cap > 0 with an array NULL. */
+rsp_status_t rsp_refine_history(rsp_refine_t s, int cap, double *relres, int *inner_iters, int *count);
+rsp_status_t rsp_refine_destroy(rsp_refine_t s);
+/* The refinement's building blocks on their own, as rsp_dot is the solvers'.
+ * dst_i = dst_type(src_i * 2^exp2) for i < n, |exp2| <= 1022, any of the four
+ * type pairs: the product is formed in fp64 (exact short of fp64's range), then
+ * rounded once to dst_type, to nearest even. Overflow gives +-inf, NaN stays
+ * NaN. fp32 denormals are read and written as they are; under rsp_set_ftz(1)
+ * an fp32 denormal read counts as a zero of its sign and an fp32 result that is
+ * denormal after rounding becomes one, as in the other fp32 kernels. Any
+ * naturally aligned pointers; 16-byte aligned ones move whole groups.
+ * d_src == d_dst is allowed when the types are equal. n = 0 does nothing.
+ * INVALID_VALUE: n < 0, a type outside the enum, exp2 out of range, a NULL
+ * pointer with n > 0, d_src == d_dst with different types. */
+rsp_status_t rsp_convert_scaled(rsp_handle_t handle, int64_t n, rsp_datatype_t src_type, const void *d_src,
+                                int exp2, rsp_datatype_t dst_type, void *d_dst);
+/* The update of a refinement step: x_old_i = x_i, then x_i = x_i + 2^exp2 *
+ * double(d_i) for i < n (|exp2| <= 1022): the product is exact, the sum is
+ * rounded once. d_x_old = NULL: x is not saved; otherwise it may not be d_x.
+ * INVALID_VALUE: n < 0, exp2 out of range, with n > 0 a NULL d_d or d_x or
+ * d_x_old == d_x. */
+rsp_status_t rsp_refine_update(rsp_handle_t handle, int64_t n, const float *d_d, int exp2, double *d_x,
+                               double *d_x_old);
+
 /* ------------------------------------------------ multi-GPU halo exchange */
 
 /* Indexed gather dst[i] = src[idx[i]] for i < n (value_type elements). The

@@ -53,6 +53,10 @@ OP_T = 1
 SOLVE_CONVERGED = 0
 SOLVE_MAX_ITERS = 1
 SOLVE_BREAKDOWN = 2
+SOLVE_STAGNATED = 3  # RSP_SOLVE_STAGNATED: rsp_refine_solve only
+REFINE_BICGSTAB = 0
+REFINE_CG = 1
+REFINE_GMRES = 2
 # Geometry of the Krylov kernels' reductions (rsp_kernels.h kKryChunk /
 # kKryMaxGrid): a workgroup sums KRY_CHUNK contiguous elements, and at most
 # KRY_MAX_GRID workgroups run (beyond KRY_CHUNK * KRY_MAX_GRID elements the
@@ -134,6 +138,13 @@ RSP_PROTOS = {
     "rsp_orthogonalize": (i32, [vp, i32, i64, i32, vp, i64, vp, C.POINTER(C.c_double)]),
     "rsp_gmres_lsq_host": (i32, [i32, i32, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
                                  C.POINTER(C.c_double)]),
+    "rsp_refine_create": (i32, [vp, vp, vp, vp, vp, i32, i32, C.POINTER(vp)]),
+    "rsp_refine_solve": (i32, [vp, vp, vp, vp, C.c_double, i32, C.c_double, i32, i32, ip, ip,
+                               C.POINTER(C.c_double), ip]),
+    "rsp_refine_history": (i32, [vp, i32, C.POINTER(C.c_double), ip, ip]),
+    "rsp_refine_destroy": (i32, [vp]),
+    "rsp_convert_scaled": (i32, [vp, i64, i32, vp, i32, i32, vp]),
+    "rsp_refine_update": (i32, [vp, i64, vp, i32, vp, vp]),
     "rsp_gather": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_scatter": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_spmat_set_local_cols": (i32, [vp, i64]),

@@ -1,6 +1,8 @@
 // api_krylov.cpp — the Krylov solvers of include/rsp.h: ILU(0)-preconditioned
 // BiCGStab, preconditioned CG and restarted flexible GMRES(m), and the building
-// blocks they expose (rsp_dot, rsp_orthogonalize, rsp_gmres_lsq_host). Host
+// blocks they expose (rsp_dot, rsp_orthogonalize, rsp_gmres_lsq_host), and
+// mixed-precision iterative refinement over them (rsp_refine_*,
+// rsp_convert_scaled, rsp_refine_update). Host
 // loops over the kernels of krylov.hip, spmv_run (rsp_api.cpp) and the
 // triangular solves (api_ilu_solve.cpp); what the solvers share is KrylovCommon.
 
@@ -648,7 +650,273 @@ static rsp_status_t orthogonalize(rsp_handle_t h, rsp_datatype_t value_type, int
     return RSP_STATUS_SUCCESS;
 }
 
+/* ------------------------------------------------- iterative refinement */
+
+static rsp_status_t ref_kernel(rsp_handle_t h, rsp::RefOp op, const rsp::RefArgs &a) {
+    const hipError_t e = h->ftz ? rsp_k_ftz::refine(op, a, h->stream) : rsp_k::refine(op, a, h->stream);
+    return e == hipSuccess ? RSP_STATUS_SUCCESS : RSP_STATUS_EXECUTION_FAILED;
+}
+
+static bool is_type(rsp_datatype_t t) { return t == RSP_R_64F || t == RSP_R_32F; }
+
+static rsp_status_t convert_scaled(rsp_handle_t h, int64_t n, rsp_datatype_t src_type, const void *d_src, int exp2,
+                                   rsp_datatype_t dst_type, void *d_dst) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (n < 0 || !is_type(src_type) || !is_type(dst_type) || exp2 < -1022 || exp2 > 1022)
+        return RSP_STATUS_INVALID_VALUE;
+    if (n > 0 && (!d_src || !d_dst)) return RSP_STATUS_INVALID_VALUE;
+    if (d_src == d_dst && src_type != dst_type && n > 0) return RSP_STATUS_INVALID_VALUE;
+    rsp::RefArgs a{};
+    a.n = n;
+    a.scale = ldexp(1.0, exp2);
+    a.src_f32 = src_type == RSP_R_32F;
+    a.dst_f32 = dst_type == RSP_R_32F;
+    a.src = d_src;
+    a.dst = d_dst;
+    return ref_kernel(h, rsp::kRefConvert, a);
+}
+
+static rsp_status_t refine_update(rsp_handle_t h, int64_t n, const float *d_d, int exp2, double *d_x,
+                                  double *d_x_old) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (n < 0 || exp2 < -1022 || exp2 > 1022) return RSP_STATUS_INVALID_VALUE;
+    if (n > 0 && (!d_d || !d_x || d_x_old == d_x)) return RSP_STATUS_INVALID_VALUE;
+    rsp::RefArgs a{};
+    a.n = n;
+    a.scale = ldexp(1.0, exp2);
+    a.src = d_d;
+    a.dst = d_x;
+    a.x_old = d_x_old;
+    return ref_kernel(h, rsp::kRefUpdate, a);
+}
+
+// One refinement: the fp64 side (r, v = A x, x_old), the fp32 right-hand side
+// and correction of the inner solve, the inner solver itself (one of the three,
+// made by its public create call over A_low) and the Krylov block and mirror
+// the residual's norm is read back through (KrylovCommon with T = fp64, M = I).
+struct rsp_refine : KrylovCommon {
+    rsp_refine_method_t method = RSP_REFINE_GMRES;
+    rsp_bicgstab_t bicgstab = nullptr;
+    rsp_cg_t cg = nullptr;
+    rsp_gmres_t gmres = nullptr;
+    double *r = nullptr, *v = nullptr, *x_old = nullptr;
+    float *r32 = nullptr, *d = nullptr;
+    std::vector<int> inner_history;  // per history entry: the inner iterations that produced that x
+    ~rsp_refine() {
+        if (bicgstab) (void)rsp_bicgstab_destroy(bicgstab);
+        if (cg) (void)rsp_cg_destroy(cg);
+        if (gmres) (void)rsp_gmres_destroy(gmres);
+    }
+};
+
+static rsp_status_t refine_create(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_low, rsp_ilu0_info_t info,
+                                  const void *d_factor_low, rsp_refine_method_t method, int restart,
+                                  rsp_refine_t *out) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!out) return RSP_STATUS_INVALID_VALUE;
+    *out = nullptr;
+    if (!A || !A_low || (info && !d_factor_low)) return RSP_STATUS_INVALID_VALUE;
+    if (A->type != RSP_R_64F || A_low->type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+    if (A->rows != A->cols || A->rows < 1 || A_low->rows != A->rows || A_low->cols != A->cols)
+        return RSP_STATUS_INVALID_VALUE;
+    if (method != RSP_REFINE_BICGSTAB && method != RSP_REFINE_CG && method != RSP_REFINE_GMRES)
+        return RSP_STATUS_INVALID_VALUE;
+    if (method == RSP_REFINE_GMRES && (restart < 1 || restart > RSP_GMRES_MAX_RESTART))
+        return RSP_STATUS_INVALID_VALUE;
+    if (!A->planned || A->plan_type != A->type) RSP_TRY(spmv_plan(h, A, A->type));
+    std::unique_ptr<rsp_refine> s(new rsp_refine);  // (a half-built one is freed on every way out, its inner solver too)
+    krylov_bind(*s, h, A, nullptr, RSP_R_64F, nullptr);
+    s->method = method;
+    switch (method) {
+        case RSP_REFINE_BICGSTAB:
+            RSP_TRY(rsp_bicgstab_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->bicgstab));
+            break;
+        case RSP_REFINE_CG:
+            RSP_TRY(rsp_cg_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->cg));
+            break;
+        default:
+            RSP_TRY(rsp_gmres_create(h, A_low, info, RSP_R_32F, d_factor_low, restart, &s->gmres));
+            break;
+    }
+    // r, v, x_old (fp64), then r32, d (fp32)
+    const size_t tb = s->tbytes(), lb = align256((size_t)s->n * sizeof(float));
+    char *at = nullptr;
+    RSP_TRY(krylov_alloc(*s, align256(rsp::kKryBlockDoubles * sizeof(double)), 3 * tb + 2 * lb,
+                         rsp::kKryScalars + 2 * (size_t)rsp::kKryMaxGrid, &at));
+    s->r = (double *)at;
+    s->v = (double *)(at + tb);
+    s->x_old = (double *)(at + 2 * tb);
+    s->r32 = (float *)(at + 3 * tb);
+    s->d = (float *)(at + 3 * tb + lb);
+    *out = s.release();
+    return RSP_STATUS_SUCCESS;
+}
+
+static rsp_status_t refine_inner(rsp_handle_t h, rsp_refine_t s, double rtol, int max_iters, int check_every,
+                                 int *iters, rsp_solve_reason_t *reason) {
+    double rel = 0.0;
+    switch (s->method) {
+        case RSP_REFINE_BICGSTAB:
+            return rsp_bicgstab_solve(h, s->bicgstab, s->r32, s->d, rtol, max_iters, check_every, iters, &rel, reason);
+        case RSP_REFINE_CG:
+            return rsp_cg_solve(h, s->cg, s->r32, s->d, rtol, max_iters, check_every, iters, &rel, reason);
+        default:
+            return rsp_gmres_solve(h, s->gmres, s->r32, s->d, rtol, max_iters, check_every, iters, &rel, reason);
+    }
+}
+
+static rsp_status_t refine_solve(rsp_handle_t h, rsp_refine_t s, const void *d_b, void *d_x, double rtol,
+                                 int max_steps, double inner_rtol, int inner_max_iters, int check_every, int *steps,
+                                 int *inner_iters, double *relres, rsp_solve_reason_t *reason) {
+    if (!h) return RSP_STATUS_NOT_INITIALIZED;
+    if (!inner_iters) return RSP_STATUS_INVALID_VALUE;
+    if (inner_max_iters < 0 || !(inner_rtol >= 0.0)) return RSP_STATUS_INVALID_VALUE;
+    RSP_TRY(krylov_solve_begin(h, s, d_b, d_x, rtol, max_steps, check_every, steps, relres, reason));
+    *inner_iters = 0;
+    s->inner_history.clear();
+    const int G = rsp::kry_grid(s->n).grid;
+    const size_t xbytes = (size_t)s->n * sizeof(double);
+    rsp::KryArgs a{};
+    a.n = s->n;
+    a.blk = s->d_blk;
+    a.b = d_b;
+    a.v = s->v;
+    a.r = s->r;
+    double *hp = s->h_pin;
+    // the one host wait of a step: the (r,r) partials (step 0: and (b,b)), as cg_solve's
+    auto residual = [&](bool bb, double *rr) -> rsp_status_t {
+        RSP_TRY(krylov_spmv(h, *s, d_x, s->v));
+        if (rsp_k::krylov(rsp::kKryCgInit, rsp::kKryF64, a, h->stream) != hipSuccess)  // r = b - v; (b,b), (r,r)
+            return RSP_STATUS_EXECUTION_FAILED;
+        if (bb)
+            RSP_CHECK_HIP(hipMemcpyAsync(hp + rsp::kKryScalars + rsp::kKryMaxGrid,
+                                         s->d_blk + rsp::kKryScalars + (size_t)rsp::kKryPartBB * rsp::kKryMaxGrid,
+                                         (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipMemcpyAsync(hp, s->d_blk, (rsp::kKryScalars + (size_t)G) * sizeof(double),
+                                     hipMemcpyDeviceToHost, h->stream));
+        RSP_CHECK_HIP(hipEventRecord(s->ev, h->stream));
+        RSP_CHECK_HIP(hipEventSynchronize(s->ev));
+        *rr = rsp::kry_combine_host(hp + rsp::kKryScalars, G);
+        return RSP_STATUS_SUCCESS;
+    };
+    auto restore = [&]() -> rsp_status_t {  // the rejected step's x gives way to the one before it
+        RSP_CHECK_HIP(hipMemcpyAsync(d_x, s->x_old, xbytes, hipMemcpyDeviceToDevice, h->stream));
+        RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+        return RSP_STATUS_SUCCESS;
+    };
+    double bnorm = 0.0, rn_prev = 0.0;
+    int inner_last = 0;
+    for (int k = 0;; k++) {
+        double rr = 0.0;
+        RSP_TRY(residual(k == 0, &rr));
+        if (k == 0) {
+            const double bb = rsp::kry_combine_host(hp + rsp::kKryScalars + rsp::kKryMaxGrid, G);
+            bnorm = sqrt(bb);
+            if (bb == 0.0) {  // x = 0 solves it
+                rsp::KryArgs z{};
+                z.n = s->n;
+                z.x = d_x;
+                if (rsp_k::krylov(rsp::kKryZero, rsp::kKryF64, z, h->stream) != hipSuccess)
+                    return RSP_STATUS_EXECUTION_FAILED;
+                RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+                *reason = RSP_SOLVE_CONVERGED;
+                return RSP_STATUS_SUCCESS;
+            }
+        }
+        const double rn = sqrt(rr), rel = rn / bnorm;
+        s->history.push_back(rel);
+        s->inner_history.push_back(inner_last);
+        if (!std::isfinite(rn) || !std::isfinite(bnorm)) {  // k = 0: b or x0 not finite; later: the correction was not
+            *reason = RSP_SOLVE_BREAKDOWN;
+            if (k > 0) RSP_TRY(restore());
+            *steps = k > 0 ? k - 1 : 0;
+            *relres = k > 0 ? s->history[k - 1] : rel;
+            return RSP_STATUS_SUCCESS;
+        }
+        if (rel <= rtol) {
+            *reason = RSP_SOLVE_CONVERGED;
+            *steps = k;
+            *relres = rel;
+            return RSP_STATUS_SUCCESS;
+        }
+        if (k > 0 && rn >= rn_prev) {  // the step gained nothing: the floor of this A, A_low and inner solve
+            RSP_TRY(restore());
+            *reason = RSP_SOLVE_STAGNATED;
+            *steps = k - 1;
+            *relres = s->history[k - 1];
+            return RSP_STATUS_SUCCESS;
+        }
+        *steps = k;
+        *relres = rel;
+        if (k == max_steps) return RSP_STATUS_SUCCESS;  // (*reason is MAX_ITERS)
+        rn_prev = rn;
+        // r32 = fp32(r * 2^-e) with ||r|| = m * 2^e, 0.5 <= m < 1; d = 0
+        int e = 0;
+        (void)frexp(rn, &e);
+        e = std::min(std::max(e, -1022), 1022);
+        rsp::RefArgs c{};
+        c.n = s->n;
+        c.scale = ldexp(1.0, -e);
+        c.src = s->r;
+        c.dst = s->r32;
+        c.zero = s->d;
+        RSP_TRY(ref_kernel(h, rsp::kRefNarrowZero, c));
+        rsp_solve_reason_t ir = RSP_SOLVE_MAX_ITERS;
+        RSP_TRY(refine_inner(h, s, inner_rtol, inner_max_iters, check_every, &inner_last, &ir));
+        *inner_iters += inner_last;
+        if (ir == RSP_SOLVE_BREAKDOWN && inner_last == 0) {  // nothing to add
+            *reason = RSP_SOLVE_BREAKDOWN;
+            RSP_CHECK_HIP(hipStreamSynchronize(h->stream));
+            return RSP_STATUS_SUCCESS;
+        }
+        RSP_TRY(refine_update(h, s->n, s->d, e, (double *)d_x, s->x_old));
+    }
+}
+
+static rsp_status_t refine_history(const rsp_refine *s, int cap, double *relres, int *inner_iters, int *count) {
+    if (!s || !count || cap < 0 || (cap > 0 && (!relres || !inner_iters))) return RSP_STATUS_INVALID_VALUE;
+    *count = (int)s->history.size();
+    for (int k = 0; k < cap && k < *count; k++) {
+        relres[k] = s->history[k];
+        inner_iters[k] = s->inner_history[k];
+    }
+    return RSP_STATUS_SUCCESS;
+}
+
 extern "C" {
+
+rsp_status_t rsp_refine_create(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_low, rsp_ilu0_info_t info,
+                               const void *d_factor_low, rsp_refine_method_t method, int restart, rsp_refine_t *s) {
+    return guarded([&] { return refine_create(h, A, A_low, info, d_factor_low, method, restart, s); });
+}
+
+rsp_status_t rsp_refine_solve(rsp_handle_t h, rsp_refine_t s, const void *d_b, void *d_x, double rtol, int max_steps,
+                              double inner_rtol, int inner_max_iters, int check_every, int *steps, int *inner_iters,
+                              double *relres, rsp_solve_reason_t *reason) {
+    return guarded([&] {
+        return refine_solve(h, s, d_b, d_x, rtol, max_steps, inner_rtol, inner_max_iters, check_every, steps,
+                            inner_iters, relres, reason);
+    });
+}
+
+rsp_status_t rsp_refine_history(rsp_refine_t s, int cap, double *relres, int *inner_iters, int *count) {
+    return refine_history(s, cap, relres, inner_iters, count);
+}
+
+rsp_status_t rsp_refine_destroy(rsp_refine_t s) {
+    if (!s) return RSP_STATUS_INVALID_VALUE;
+    delete s;
+    return RSP_STATUS_SUCCESS;
+}
+
+rsp_status_t rsp_convert_scaled(rsp_handle_t h, int64_t n, rsp_datatype_t src_type, const void *d_src, int exp2,
+                                rsp_datatype_t dst_type, void *d_dst) {
+    return guarded([&] { return convert_scaled(h, n, src_type, d_src, exp2, dst_type, d_dst); });
+}
+
+rsp_status_t rsp_refine_update(rsp_handle_t h, int64_t n, const float *d_d, int exp2, double *d_x, double *d_x_old) {
+    return guarded([&] { return refine_update(h, n, d_d, exp2, d_x, d_x_old); });
+}
 
 rsp_status_t rsp_bicgstab_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
                                  rsp_datatype_t precond_type, const void *d_factor, rsp_bicgstab_t *s) {

@@ -1,7 +1,9 @@
 // krylov.hip — the vector side of the ILU(0)-preconditioned BiCGStab iteration
 // (rsp_bicgstab_*), of preconditioned CG (rsp_cg_*: the cg_* kernels) and of
 // restarted flexible GMRES (rsp_gmres_*, rsp_orthogonalize: the gm_* kernels),
-// both described where they start, and rsp_dot, for gfx950. The SpMVs and triangular solves of an iteration are the library's
+// both described where they start, rsp_dot, and the element-wise kernels of
+// mixed-precision iterative refinement (rsp_refine_*, rsp_convert_scaled,
+// rsp_refine_update: the ref_* kernels), for gfx950. The SpMVs and triangular solves of an iteration are the library's
 // existing entry points; everything between them is here. BiCGStab, five
 // launches per iteration:
 //
@@ -867,6 +869,119 @@ __global__ __launch_bounds__(kKryThreads) void gm_combine(long long n, long long
     }
 }
 
+// -------------------------------------------------- iterative refinement
+//
+// Mixed-precision refinement (rsp_refine_*) and its building blocks
+// (rsp_convert_scaled, rsp_refine_update). A step's residual r = b - A x is
+// cg_init at fp64; the two kernels between it and the fp32 inner solve are
+//
+//   ref_convert<double, float, ZERO>  r32 = fp32(r * 2^-e), d = 0   (8n read, 8n written)
+//   ref_update                        x_old = x; x = x + 2^e * double(d)
+//
+// scale = 2^exp2 is an fp64 value and every product with it is exact short of
+// fp64's range, so an element is rounded once, to its destination type (to
+// nearest even: the conversion's and the addition's own rounding). A thread
+// moves four elements per step whatever the types: one float4, or two double2.
+// In the FTZ build an fp32 denormal read counts as a zero of its sign and an
+// fp32 result that is denormal after rounding becomes one, decided on the fp64
+// value, so no conversion instruction's own denormal mode is relied on.
+
+__device__ __forceinline__ double ref_widen(float s) {
+#ifdef RSP_FTZ_BUILD
+    if (__builtin_fabsf(s) < 0x1p-126f) s = __builtin_copysignf(0.0f, s);
+#endif
+    return (double)s;
+}
+
+template <typename D>
+__device__ __forceinline__ D ref_narrow(double v);
+template <>
+__device__ __forceinline__ double ref_narrow<double>(double v) {
+    return v;
+}
+template <>
+__device__ __forceinline__ float ref_narrow<float>(double v) {
+    float f = (float)v;
+#ifdef RSP_FTZ_BUILD
+    // below 2^-126 - 2^-150 the rounded value is denormal (the tie rounds to the even 2^-126)
+    const double a = __builtin_fabs(v);
+    if (a < 0x1p-126) f = __builtin_copysignf(a >= 0x1p-126 - 0x1p-150 ? 0x1p-126f : 0.0f, f);
+#endif
+    return f;
+}
+
+// four elements at j (cnt of them in range) as fp64, and back
+template <typename T, bool VEC>
+__device__ __forceinline__ void ref_ld4(const T *p, long long j, int cnt, double (&out)[4]) {
+    if constexpr (sizeof(T) == 4) {
+        const Grp<T> g = ld<T, VEC>(p, j, cnt);
+#pragma unroll
+        for (int k = 0; k < 4; k++) out[k] = ref_widen(g.e[k]);
+    } else {
+        const Grp<T> lo = ld<T, VEC>(p, j, cnt < 2 ? cnt : 2);
+        Grp<T> hi;
+        hi.e[0] = hi.e[1] = T(0);
+        if (cnt > 2) hi = ld<T, VEC>(p, j + 2, cnt - 2);
+        out[0] = lo.e[0];
+        out[1] = lo.e[1];
+        out[2] = hi.e[0];
+        out[3] = hi.e[1];
+    }
+}
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void ref_st4(T *p, long long j, int cnt, const T (&v)[4]) {
+    if constexpr (sizeof(T) == 4) {
+        Grp<T> g;
+#pragma unroll
+        for (int k = 0; k < 4; k++) g.e[k] = v[k];
+        st<T, VEC>(p, j, cnt, g);
+    } else {
+        Grp<T> lo, hi;
+        lo.e[0] = v[0];
+        lo.e[1] = v[1];
+        hi.e[0] = v[2];
+        hi.e[1] = v[3];
+        st<T, VEC>(p, j, cnt < 2 ? cnt : 2, lo);
+        if (cnt > 2) st<T, VEC>(p, j + 2, cnt - 2, hi);
+    }
+}
+
+// dst = D(src * scale) [ZERO: and zero = 0]. src == dst is allowed (S == D): a
+// thread reads its four elements before it writes them, so no __restrict__.
+template <typename S, typename D, bool VEC, bool ZERO>
+__global__ __launch_bounds__(kKryThreads) void ref_convert(long long n, long long chunk, double scale, const S *src,
+                                                           D *dst, float *zero) {
+    KRY_FOR_GROUPS(float, n, chunk) {
+        double w[4];
+        ref_ld4<S, VEC>(src, j, cnt, w);
+        D o[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) o[k] = ref_narrow<D>(w[k] * scale);
+        ref_st4<D, VEC>(dst, j, cnt, o);
+        if constexpr (ZERO) {
+            const float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            ref_st4<float, VEC>(zero, j, cnt, z);
+        }
+    }
+}
+
+// x_old = x (SAVE); x = x + scale * double(d)
+template <bool VEC, bool SAVE>
+__global__ __launch_bounds__(kKryThreads) void ref_update(long long n, long long chunk, double scale,
+                                                          const float *__restrict__ d, double *__restrict__ x,
+                                                          double *__restrict__ x_old) {
+    KRY_FOR_GROUPS(float, n, chunk) {
+        double dd[4], xx[4];
+        ref_ld4<float, VEC>(d, j, cnt, dd);
+        ref_ld4<double, VEC>(x, j, cnt, xx);
+        if constexpr (SAVE) ref_st4<double, VEC>(x_old, j, cnt, xx);
+#pragma unroll
+        for (int k = 0; k < 4; k++) xx[k] = xx[k] + scale * dd[k];
+        ref_st4<double, VEC>(x, j, cnt, xx);
+    }
+}
+
 inline bool aligned16(std::initializer_list<const void *> ps) {
     uintptr_t m = 0;
     for (const void *p : ps) m |= (uintptr_t)p;
@@ -992,11 +1107,63 @@ hipError_t gm_launch(GmOp op, const GmArgs &a, hipStream_t s) {
         default:
             return hipErrorInvalidValue;
     }
-#undef KRY_LAUNCH
     return hipGetLastError();
 }
 
+template <typename S, typename D>
+hipError_t ref_convert_launch(const RefArgs &a, bool zero, hipStream_t s) {
+    const KryGrid kg = kry_grid(a.n);
+    const dim3 grid(kg.grid), block(kKryThreads);
+    const S *src = (const S *)a.src;
+    D *dst = (D *)a.dst;
+    if (zero) {
+        if constexpr (sizeof(S) == 8 && sizeof(D) == 4)
+            KRY_LAUNCH(aligned16({src, dst, a.zero}), (ref_convert<S, D, true, true>),
+                       (ref_convert<S, D, false, true>), a.n, kg.chunk, a.scale, src, dst, a.zero);
+        else
+            return hipErrorInvalidValue;
+    } else {
+        KRY_LAUNCH(aligned16({src, dst}), (ref_convert<S, D, true, false>), (ref_convert<S, D, false, false>), a.n,
+                   kg.chunk, a.scale, src, dst, (float *)nullptr);
+    }
+    return hipGetLastError();
+}
+
+hipError_t ref_launch(RefOp op, const RefArgs &a, hipStream_t s) {
+    switch (op) {
+        case kRefConvert:
+            if (a.src_f32)
+                return a.dst_f32 ? ref_convert_launch<float, float>(a, false, s)
+                                 : ref_convert_launch<float, double>(a, false, s);
+            return a.dst_f32 ? ref_convert_launch<double, float>(a, false, s)
+                             : ref_convert_launch<double, double>(a, false, s);
+        case kRefNarrowZero:
+            return ref_convert_launch<double, float>(a, true, s);
+        case kRefUpdate: {
+            const KryGrid kg = kry_grid(a.n);
+            const dim3 grid(kg.grid), block(kKryThreads);
+            const float *d = (const float *)a.src;
+            double *x = (double *)a.dst;
+            if (a.x_old)
+                KRY_LAUNCH(aligned16({d, x, a.x_old}), (ref_update<true, true>), (ref_update<false, true>), a.n,
+                           kg.chunk, a.scale, d, x, a.x_old);
+            else
+                KRY_LAUNCH(aligned16({d, x}), (ref_update<true, false>), (ref_update<false, false>), a.n, kg.chunk,
+                           a.scale, d, x, (double *)nullptr);
+            return hipGetLastError();
+        }
+        default:
+            return hipErrorInvalidValue;
+    }
+}
+#undef KRY_LAUNCH
+
 }  // namespace
+
+hipError_t refine(RefOp op, const RefArgs &a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    return ref_launch(op, a, s);
+}
 
 hipError_t gmres(GmOp op, int type, const GmArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;

@@ -7,7 +7,7 @@
 //   csr_transpose.cpp     the pattern transposer (csr_transpose.h; no HIP calls)
 //   api_ilu_analysis.cpp  ILU(0) analysis, the solve plans, the plan queries
 //   api_ilu_solve.cpp     factor and triangular solves, flow give-up recovery
-//   api_krylov.cpp        BiCGStab, CG, GMRES, rsp_dot, rsp_orthogonalize
+//   api_krylov.cpp        BiCGStab, CG, GMRES, rsp_dot, rsp_orthogonalize, iterative refinement
 #pragma once
 
 #include "rsp.h"

@@ -590,6 +590,26 @@ inline double kry_combine_host(const double *part, int g) {
     return ((w[0] + w[1]) + w[2]) + w[3];
 }
 
+// Iterative refinement (krylov.hip ref_* kernels; rsp_refine_*, rsp_convert_scaled,
+// rsp_refine_update): element-wise kernels on the same grid and chunks, no
+// reduction. scale = 2^exp2 as an fp64 value: a product with it is exact short
+// of fp64's range, so every element is rounded once, to its destination type.
+// The residual of a refinement step is kKryCgInit at kKryF64.
+enum RefOp {
+    kRefConvert,     // dst_i = dst_type(src_i * scale), any of the four type pairs (src == dst: equal types)
+    kRefNarrowZero,  // dst_i (fp32) = fp32(src_i (fp64) * scale) and zero_i (fp32) = 0, one pass
+    kRefUpdate       // x_old_i = x_i (x_old null: not saved); x_i = x_i + scale * double(d_i)
+};
+struct RefArgs {
+    long long n;
+    double scale;
+    int src_f32, dst_f32;  // kRefConvert: 1 = fp32, 0 = fp64
+    const void *src;       // kRefUpdate: d (fp32)
+    void *dst;             // kRefUpdate: x (fp64)
+    float *zero;           // kRefNarrowZero: d
+    double *x_old;         // kRefUpdate, may be null
+};
+
 // Restarted flexible GMRES (krylov.hip gm_* kernels, rsp_gmres_*,
 // rsp_orthogonalize): the same grid, chunks and partials as above. Its device
 // block, all fp64: a head of scalars and the estimates (what a mid-cycle check
@@ -711,6 +731,7 @@ RSP_HD inline int gmres_lsq(double *col, int j, double *cs, double *sn, double *
     void warm_ilu();                                                                            \
     hipError_t krylov(rsp::KryOp op, int type, const rsp::KryArgs &a, hipStream_t s);           \
     hipError_t gmres(rsp::GmOp op, int type, const rsp::GmArgs &a, hipStream_t s);              \
+    hipError_t refine(rsp::RefOp op, const rsp::RefArgs &a, hipStream_t s);                     \
     void warm_krylov();                                                                         \
     }
 

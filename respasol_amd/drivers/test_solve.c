@@ -1,6 +1,7 @@
 /*
- * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) / CG driver (built
- * as `test_solve`).
+ * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) / CG driver, with
+ * --refine the same inside mixed-precision iterative refinement (built as
+ * `test_solve`).
  * No GPU counterpart in the reference; shaped like its direct-solver drivers
  * (Pardiso/test_pardiso.c): b = 1 (:107), solve, relative residual ||b - A x||
  * / ||b|| recomputed on the host (:258-274).
@@ -8,7 +9,7 @@
  *   test_solve <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32]
  *              [--precond=fp64|fp32|none] [--ftz] [--rtol=R] [--maxit=N]
  *              [--full-symmetric] [--dump=FILE] [--method=bicgstab|gmres|cg]
- *              [--restart=M]
+ *              [--restart=M] [--refine[=inner_rtol]]
  *
  * Flow: load as test_ilu0 does (outputbase 0); iteration values in --prec;
  * b = 1, x0 = 0; [timed "Symbolic"] ILU analysis; [timed "Numeric"]
@@ -23,6 +24,12 @@
  * (rsp_host_spmv_f64 on the file's fp64 values), not the recurrence's.
  * Exit 0 for any reason code (converged, max iterations, breakdown);
  * non-zero only on a status error. --dump writes x (binary, --prec type).
+ * --refine (needs --prec=fp64 and --precond=fp32 or none, else exit 2): the
+ * values are narrowed to fp32 on the device (rsp_convert_scaled), the factor is
+ * fp32 and the solve is rsp_refine_solve — fp64 residuals and updates around
+ * all-fp32 solves by --method to inner_rtol (default 1e-4), each of at most
+ * --maxit iterations, at most 50 steps; "Iterations" is then the inner
+ * iterations of all steps, and two more lines follow the report.
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -68,11 +75,15 @@ int main(int argc, char **argv) {
                 "  %s <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32] [--precond=fp64|fp32|none]\n"
                 "     [--ftz] [--rtol=R] [--maxit=N] [--full-symmetric] [--dump=FILE]\n"
                 "     [--method=bicgstab|gmres|cg] [--restart=M]\n"
+                "     [--refine[=inner_rtol]]\n"
                 "  solves A x = 1 from x0 = 0 by ILU(0)-preconditioned BiCGStab.\n"
                 "  --method=gmres: by restarted flexible GMRES(M) instead (--restart, default 30).\n"
                 "  --method=cg: by preconditioned conjugate gradients (A symmetric positive definite).\n"
                 "  A symmetric file loads as its lower triangle unless --full-symmetric is given\n"
-                "  or --method=cg, which needs both triangles, is.\n",
+                "  or --method=cg, which needs both triangles, is.\n"
+                "  --refine: mixed-precision iterative refinement, fp64 residuals around all-fp32\n"
+                "  solves by --method to inner_rtol (default 1e-4); needs --prec=fp64 and\n"
+                "  --precond=fp32 or none.\n",
                 argv[0]);
         return 2;
     }
@@ -86,6 +97,9 @@ int main(int argc, char **argv) {
     const int gmres = method && strcmp(method, "gmres") == 0;
     const int cg = method && strcmp(method, "cg") == 0;
     const int restart = restart_s && *restart_s ? atoi(restart_s) : 30;
+    const char *refine_s = drv_flag(argc, argv, 2, "refine");
+    const int refine = refine_s != NULL;
+    const double inner_rtol = refine_s && *refine_s ? atof(refine_s) : 1e-4;
     if (method && *method && !gmres && !cg && strcmp(method, "bicgstab") != 0) {
         fprintf(stderr, "Error: --method is bicgstab, gmres or cg\n");
         return 2;
@@ -99,6 +113,11 @@ int main(int argc, char **argv) {
     const int maxit = maxit_s && *maxit_s ? atoi(maxit_s) : 1000;
     if (use_m && fp32 && !m32) {
         fprintf(stderr, "Error: --precond=fp64 is wider than --prec=fp32\n");
+        return 2;
+    }
+
+    if (refine && (fp32 || (use_m && !m32))) {
+        fprintf(stderr, "Error: --refine needs --prec=fp64 and --precond=fp32 or none\n");
         return 2;
     }
 
@@ -173,7 +192,18 @@ int main(int argc, char **argv) {
     rsp_bicgstab_t solver = NULL;
     rsp_gmres_t gsolver = NULL;
     rsp_cg_t csolver = NULL;
-    if (gmres)
+    rsp_refine_t rsolver = NULL;
+    rsp_spmat_t mat_low = NULL;
+    void *d_vlow = NULL;
+    int steps = 0;
+    if (refine) {
+        HIP_OR_FAIL(hipMalloc(&d_vlow, (size_t)(nnz_s ? nnz_s : 1) * sizeof(float)));
+        RSP_OR_FAIL(rsp_convert_scaled(handle, nnz_s, RSP_R_64F, d_v, 0, RSP_R_32F, d_vlow));
+        RSP_OR_FAIL(rsp_create_csr(&mat_low, n, n, A.nnz, d_rp, d_ci, d_vlow, RSP_R_32F));
+        RSP_OR_FAIL(rsp_refine_create(handle, mat, mat_low, info, d_m,
+                                      gmres ? RSP_REFINE_GMRES : (cg ? RSP_REFINE_CG : RSP_REFINE_BICGSTAB), restart,
+                                      &rsolver));
+    } else if (gmres)
         RSP_OR_FAIL(rsp_gmres_create(handle, mat, info, mt, d_m, restart, &gsolver));
     else if (cg)
         RSP_OR_FAIL(rsp_cg_create(handle, mat, info, mt, d_m, &csolver));
@@ -183,7 +213,10 @@ int main(int argc, char **argv) {
     double relres = 0.0;
     rsp_solve_reason_t reason = RSP_SOLVE_MAX_ITERS;
     HIP_OR_FAIL(hipEventRecord(start, NULL));
-    if (gmres)
+    if (refine)
+        RSP_OR_FAIL(rsp_refine_solve(handle, rsolver, d_b, d_x, rtol, 50, inner_rtol, maxit, 1, &steps, &iters, &relres,
+                                     &reason));
+    else if (gmres)
         RSP_OR_FAIL(rsp_gmres_solve(handle, gsolver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
     else if (cg)
         RSP_OR_FAIL(rsp_cg_solve(handle, csolver, d_b, d_x, rtol, maxit, 1, &iters, &relres, &reason));
@@ -208,6 +241,7 @@ int main(int argc, char **argv) {
     printf(fp32 ? "SINGLE PRECISION ITERATION IN  MILLISECONDS\n " : "DOUBLE PRECISION ITERATION IN  MILLISECONDS\n ");
     printf("Symbolic = %f\n Numeric = %f \n Solve = %f\n Iterations = %d\n Reason = %d\n Relative residual = %e\n",
            time_symbolic, time_numeric, time_solve, iters, (int)reason, sqrt(rn) / sqrt(bn));
+    if (refine) printf(" Refinement steps = %d\n Inner iterations = %d\n", steps, iters);
 
     if (dump && *dump) {
         FILE *fp = fopen(dump, "wb");
@@ -219,7 +253,11 @@ int main(int argc, char **argv) {
 
     hipEventDestroy(start);
     hipEventDestroy(stop);
-    if (gmres)
+    if (refine) {
+        rsp_refine_destroy(rsolver);
+        rsp_destroy_spmat(mat_low);
+        hipFree(d_vlow);
+    } else if (gmres)
         rsp_gmres_destroy(gsolver);
     else if (cg)
         rsp_cg_destroy(csolver);

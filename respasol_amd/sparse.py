@@ -29,6 +29,12 @@ Mapping to the reference's cuSPARSE usage:
                          symmetric positive definite A (rsp_cg_*)
   GMRES                  restarted flexible GMRES(m) on the same operators
                          (rsp_gmres_*)
+  Refine                 mixed-precision iterative refinement: fp64 residuals
+                         and updates around an all-fp32 BiCGStab / CG / GMRES
+                         solve of the correction (rsp_refine_*)
+  convert_scaled         dst = dst_type(src * 2^exp2), one rounding
+                         (rsp_convert_scaled)
+  refine_update          x_old = x; x += 2^exp2 * double(d) (rsp_refine_update)
   dot                    cublasDdot on the solver's reduction (rsp_dot)
   orthogonalize          one twice-applied Gram-Schmidt step of GMRES
                          (rsp_orthogonalize)
@@ -418,12 +424,17 @@ class Ilu0:
 class SolveResult:
     """What BiCGStab.solve, CG.solve and GMRES.solve return: x (the solution tensor), iters, relres
     (recurrence ||r|| / ||b|| at the last check), reason (_lib.SOLVE_*) and
-    history (relres after each checked iteration)."""
+    history (relres after each checked iteration). Refine.solve: iters is the
+    sum of the inner solves' iterations, steps the accepted corrections, relres
+    the true ||b - A x|| / ||b|| of x, history its value at every step (a
+    rejected one included) and inner_history, as long, the inner iterations
+    that produced each step's x (None for the other solvers, as steps is)."""
 
-    __slots__ = ("x", "iters", "relres", "reason", "history")
+    __slots__ = ("x", "iters", "relres", "reason", "history", "steps", "inner_history")
 
-    def __init__(self, x, iters, relres, reason, history):
+    def __init__(self, x, iters, relres, reason, history, steps=None, inner_history=None):
         self.x, self.iters, self.relres, self.reason, self.history = x, iters, relres, reason, history
+        self.steps, self.inner_history = steps, inner_history
 
     @property
     def converged(self) -> bool:
@@ -595,6 +606,93 @@ class GMRES:
             pass
 
 
+class Refine:
+    """Mixed-precision iterative refinement (rsp_refine_*): fp64 residual and
+    update around an all-fp32 inner solve of A_low d = r by `method`
+    ("bicgstab", "cg" or "gmres" with `restart`). A is the fp64 matrix, A_low an
+    fp32 SpMat over the same pattern (values narrowed, e.g. by convert_scaled);
+    `ilu` (analysed) with its fp32 `factor_low` is the inner preconditioner, or
+    M = I without. A, A_low, ilu and factor_low are kept alive."""
+
+    CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
+    STAGNATED = _lib.SOLVE_STAGNATED
+    METHODS = {"bicgstab": _lib.REFINE_BICGSTAB, "cg": _lib.REFINE_CG, "gmres": _lib.REFINE_GMRES}
+
+    def __init__(self, handle: Handle, A: SpMat, A_low: SpMat, ilu: Ilu0 | None = None,
+                 factor_low: torch.Tensor | None = None, method: str = "gmres", restart: int = 30):
+        if method not in self.METHODS:
+            raise ValueError("method is bicgstab, cg or gmres")
+        if ilu is not None and factor_low is None:
+            raise ValueError("an ILU(0) preconditioner needs its factored values")
+        if factor_low is not None and factor_low.dtype != torch.float32:
+            raise TypeError("factor_low must be float32")
+        self.handle, self.A, self.A_low, self.ilu, self.factor_low = handle, A, A_low, ilu, factor_low
+        self.method, self.restart = method, int(restart)
+        self._s = C.c_void_p()
+        check(rsp.rsp_refine_create(handle.ptr, A._mat, A_low._mat, ilu._info if ilu is not None else None,
+                                    _ptr(factor_low) if ilu is not None else None, self.METHODS[method],
+                                    self.restart, C.byref(self._s)), "rsp_refine_create")
+
+    def solve(self, b: torch.Tensor, x0: torch.Tensor | None = None, rtol: float = 1e-10, max_steps: int = 20,
+              inner_rtol: float = 1e-4, inner_max_iters: int = 1000, check_every: int = 1) -> SolveResult:
+        """Solve A x = b from x0 (default 0) in fp64; x0 is not modified."""
+        if b.dtype != torch.float64 or b.numel() != self.A.m:
+            raise ValueError("b has the wrong dtype or length")
+        if x0 is not None and (x0.dtype != torch.float64 or x0.numel() != self.A.m):
+            raise ValueError("x0 has the wrong dtype or length")
+        with torch.cuda.stream(self.handle.stream):
+            x = torch.zeros_like(b) if x0 is None else x0.clone()
+        steps, inner, reason, rel = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(rsp.rsp_refine_solve(self.handle.ptr, self._s, _ptr(b), _ptr(x), float(rtol), int(max_steps),
+                                   float(inner_rtol), int(inner_max_iters), int(check_every), C.byref(steps),
+                                   C.byref(inner), C.byref(rel), C.byref(reason)), "rsp_refine_solve")
+        count = C.c_int()
+        check(rsp.rsp_refine_history(self._s, 0, None, None, C.byref(count)), "rsp_refine_history")
+        hist = (C.c_double * max(count.value, 1))()
+        its = (C.c_int * max(count.value, 1))()
+        check(rsp.rsp_refine_history(self._s, count.value, hist, its, C.byref(count)), "rsp_refine_history")
+        return SolveResult(x, inner.value, rel.value, reason.value, list(hist[:count.value]), steps.value,
+                           list(its[:count.value]))
+
+    def close(self) -> None:
+        if self._s:
+            rsp.rsp_refine_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def convert_scaled(handle: Handle, src: torch.Tensor, dst: torch.Tensor | None = None, exp2: int = 0,
+                   dtype: torch.dtype | None = None) -> torch.Tensor:
+    """dst = dst.dtype(src * 2^exp2), the product in fp64 and one rounding
+    (rsp_convert_scaled); dst defaults to a new tensor of `dtype` (default
+    float32). dst may be src itself."""
+    if dst is None:
+        dst = torch.empty(src.numel(), dtype=dtype or torch.float32, device=src.device)
+    if src.dtype not in _DT or dst.dtype not in _DT or dst.numel() < src.numel():
+        raise ValueError("convert_scaled: float64 / float32 tensors, dst at least as long as src")
+    check(rsp.rsp_convert_scaled(handle.ptr, src.numel(), _DT[src.dtype], _ptr(src), int(exp2), _DT[dst.dtype],
+                                 _ptr(dst)), "rsp_convert_scaled")
+    return dst
+
+
+def refine_update(handle: Handle, d: torch.Tensor, x: torch.Tensor, exp2: int = 0,
+                  x_old: torch.Tensor | None = None) -> torch.Tensor:
+    """x_old = x (if given), then x += 2^exp2 * double(d) in place
+    (rsp_refine_update); d float32, x and x_old float64."""
+    if d.dtype != torch.float32 or x.dtype != torch.float64 or x.numel() != d.numel():
+        raise ValueError("refine_update: d float32 and x float64 of one length")
+    if x_old is not None and (x_old.dtype != torch.float64 or x_old.numel() < x.numel()):
+        raise ValueError("refine_update: x_old float64, as long as x")
+    check(rsp.rsp_refine_update(handle.ptr, x.numel(), _ptr(d), int(exp2), _ptr(x), _ptr(x_old)),
+          "rsp_refine_update")
+    return x
+
+
 def dot(handle: Handle, x: torch.Tensor, y: torch.Tensor) -> float:
     """sum x_i y_i in fp64, in an order fixed by the length (rsp_dot)."""
     if x.dtype != y.dtype or x.dtype not in _DT or x.numel() != y.numel():
@@ -679,5 +777,6 @@ def csr_transpose_host(rowptr, colidx, n_cols: int):
     return t_rp, t_ci, perm
 
 
-__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "CG", "GMRES", "SolveResult", "dot", "orthogonalize", "upload_csr",
-           "gather", "scatter", "csr2csc", "csr_transpose_host", "RspError"]
+__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "CG", "GMRES", "Refine", "SolveResult", "dot", "orthogonalize",
+           "convert_scaled", "refine_update", "upload_csr", "gather", "scatter", "csr2csc", "csr_transpose_host",
+           "RspError"]

@@ -5,6 +5,7 @@ a narrower preconditioner reach the same residual in less time?
     python scripts/bench_solve.py [--names A,B] [--scale S] [--rtol R] [--maxit N]
                                   [--method bicgstab|gmres|cg] [--restart M]
                                   [--both-triangles] [--out FILE.jsonl]
+                                  [--refine] [--inner-rtol R]
 
 Per matrix (b = 1, x0 = 0, fp64 iteration) and per configuration
     fp64      fp64 ILU(0) factor and solves
@@ -36,6 +37,16 @@ with a narrower preconditioner) and the read-backs. A surrogate expanded this
 way is not guaranteed positive definite: BREAKDOWN is then the result.
 --both-triangles gives BiCGStab and GMRES the same expanded matrices (and the
 same skipping), for a comparison on equal systems.
+
+--refine: instead of the three configurations, one line per matrix for
+mixed-precision iterative refinement (rsp_refine_*: fp64 residuals and updates
+around all-fp32 solves by --method to --inner-rtol, default 1e-4, each of at
+most --maxit iterations; fp32 matrix, fp32 ILU(0), no FTZ): steps,
+inner_iters, reason (3 = stagnated), relres and true_relres of the refined x
+and refine_ms, and beside it the fp64 iteration under the same fp32
+preconditioner by the same method (base_iters, base_reason, base_true_relres,
+base_ms); ratio = refine_ms / base_ms. Times as above (median of 5 after one
+warm-up).
 """
 from __future__ import annotations
 
@@ -52,7 +63,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from respasol_amd import _lib, csr  # noqa: E402
-from respasol_amd.sparse import CG, GMRES, BiCGStab, Handle, Ilu0, RspError, SpMat, upload_csr  # noqa: E402
+from respasol_amd.sparse import (CG, GMRES, BiCGStab, Handle, Ilu0, Refine, RspError, SpMat,  # noqa: E402
+                                 convert_scaled, upload_csr)
 
 CONFIGS = (("fp64", torch.float64, False), ("fp32", torch.float32, False), ("fp32ftz", torch.float32, True))
 
@@ -144,6 +156,50 @@ def run_one(name, A, cfg, rtol, maxit, method="bicgstab", restart=30):
         h.close()
 
 
+def run_refine(name, A, rtol, maxit, method="bicgstab", restart=30, inner_rtol=1e-4):
+    """The refined solve and, beside it, the fp64 iteration under the same fp32 factor."""
+    rec = {"matrix": name, "config": "refine", "method": method, "n": A.m, "nnz": A.nnz_stored,
+           "inner_rtol": inner_rtol}
+    h = Handle()
+    rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
+    mat = SpMat(h, rp, ci, va, A.n)
+    low = convert_scaled(h, va, exp2=0, dtype=torch.float32)
+    mat_low = SpMat(h, rp, ci, low, A.n)
+    ilu = Ilu0(h, rp, ci)
+    solver = base = None
+    try:
+        ilu.analysis()
+        fac = low.clone()  # the factor overwrites it: never A_low's own values
+        ilu.factor(fac)
+        try:
+            solver = Refine(h, mat, mat_low, ilu, fac, method=method, restart=restart)
+            base = (GMRES(h, mat, ilu, fac, restart=restart) if method == "gmres"
+                    else CG(h, mat, ilu, fac) if method == "cg" else BiCGStab(h, mat, ilu, fac))
+        except RspError as e:
+            rec["error"] = str(e)
+            return rec
+        b = torch.ones(A.m, dtype=torch.float64, device="cuda")
+        kw = dict(rtol=rtol, inner_rtol=inner_rtol, inner_max_iters=maxit)
+        res = solver.solve(b, **kw)  # warm-up
+        rec.update(steps=res.steps, inner_iters=res.iters, reason=res.reason, relres=res.relres,
+                   true_relres=true_relres(A, res.x.cpu().numpy()))
+        rec["refine_ms"] = timed_ms(lambda: solver.solve(b, **kw))
+        bres = base.solve(b, rtol=rtol, max_iters=maxit)  # warm-up
+        rec.update(base_iters=bres.iters, base_reason=bres.reason,
+                   base_true_relres=true_relres(A, bres.x.cpu().numpy()))
+        rec["base_ms"] = timed_ms(lambda: base.solve(b, rtol=rtol, max_iters=maxit))
+        rec["ratio"] = rec["refine_ms"] / rec["base_ms"] if rec["base_ms"] > 0 else 0.0
+        return rec
+    finally:
+        for s in (solver, base):
+            if s is not None:
+                s.close()
+        ilu.close()
+        mat_low.close()
+        mat.close()
+        h.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--names", default="", help="comma-separated surrogates (default: the 21 moderate ones)")
@@ -156,6 +212,9 @@ def main(argv=None):
                     help="symmetric surrogates only, expanded to both triangles (implied by --method cg)")
     ap.add_argument("--configs", default="", help="comma-separated subset of fp64,fp32,fp32ftz")
     ap.add_argument("--out", default="", help="also append the records to this file")
+    ap.add_argument("--refine", action="store_true",
+                    help="mixed-precision iterative refinement beside the fp64 iteration under the fp32 factor")
+    ap.add_argument("--inner-rtol", type=float, default=1e-4, help="--refine: the inner solves' rtol")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_solve.py needs an MI355X: there is no CPU fallback")
@@ -168,6 +227,13 @@ def main(argv=None):
                 print(f"# {name}: not symmetric, skipped", file=sys.stderr, flush=True)
                 continue
             A = both_triangles(A)
+        if args.refine:
+            line = json.dumps(run_refine(name, A, args.rtol, args.maxit, args.method, args.restart, args.inner_rtol))
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+            continue
         for cfg in CONFIGS:
             if args.configs and cfg[0] not in args.configs.split(","):
                 continue
