@@ -546,6 +546,89 @@ rsp_status_t rsp_convert_scaled(rsp_handle_t handle, int64_t n, rsp_datatype_t s
 rsp_status_t rsp_refine_update(rsp_handle_t handle, int64_t n, const float *d_d, int exp2, double *d_x,
                                double *d_x_old);
 
+/* ------------------- Chebyshev polynomial preconditioner (rsp_cheby_*)
+ *
+ * A preconditioner made of rsp_spmv alone, beside the ILU(0) one: z = M^-1 r =
+ * p_k(D^-1 A) D^-1 r, p_k the polynomial of the Chebyshev iteration on
+ * [lmin, lmax] started from zero, so that 1 - x p_k(x) = T_k((theta - x) /
+ * delta) / T_k(sigma) (T_k the Chebyshev polynomial). No analysis, no levels,
+ * no flow launch (nothing can give up a wait), no dot product. P is the value
+ * type of the matrix it is built on; dinv is the inverse diagonal
+ * (RSP_CHEBY_SCALE_JACOBI) or all ones (RSP_CHEBY_SCALE_NONE: the product with
+ * it is skipped). The degree k >= 1 counts terms: k - 1 rsp_spmv per apply;
+ * k = 1 is the scaled Jacobi preconditioner.
+ *
+ * Coefficients, on the host in fp64 without fused multiply-add, in this order,
+ * then rounded once to P:
+ *
+ *   theta = (lmax + lmin) / 2;  delta = (lmax - lmin) / 2;  sigma = theta / delta
+ *   rho_0 = 1 / sigma;          c0 = 1 / theta
+ *   j = 1 .. k-1:  rho_j = 1 / (2*sigma - rho_{j-1});  a_j = rho_j * rho_{j-1};  b_j = 2 * rho_j / delta
+ *
+ * The apply keeps r unchanged and needs r != z; d and w are work vectors of the
+ * object; every product and sum is rounded to P:
+ *
+ *   d_i = c0 * (dinv_i * r_i);  z_i = d_i;  w_i = r_i          (k = 1: only z is written)
+ *   j = 1 .. k-1:
+ *       w = w - A d                      rsp_spmv(alpha = -1, A, d, beta = 1, w)
+ *       t = dinv_i * w_i;  d_i = (a_j * d_i) + (b_j * t);  z_i = z_i + d_i
+ *
+ * The kernels between the products are element-wise, so the result is the bits
+ * of that restatement over rsp_spmv's canonical order, for any alignment.
+ * Per apply, in vectors of P beside the k - 1 rsp_spmv: the first kernel reads
+ * 2 and writes 3, a step reads 4 and writes 2 (the last: 1); without scaling
+ * one read less each.
+ *
+ * Set-up (one kernel): diag_i = the sum in P, in storage order, of the stored
+ * entries of row i with column i (duplicates and unsorted rows are legal);
+ * dinv_i = P(1) / diag_i; g_i = (sum_j |double(a_ij)| in fp64, storage order) /
+ * |double(diag_i)| (NONE: / 1); lmax = max_i g_i, Gershgorin's bound on the
+ * spectrum of D^-1 A, and lmin = lmax / ratio. For a symmetric positive
+ * definite A the bound is guaranteed, which keeps p_k positive on the whole
+ * spectrum: M is positive definite, as rsp_cg_* needs. An estimated lmax that
+ * falls short makes M indefinite (CG then ends in BREAKDOWN); callers who know
+ * better bounds set them. */
+#define RSP_CHEBY_MAX_DEGREE 64
+typedef enum { RSP_CHEBY_SCALE_NONE = 0, RSP_CHEBY_SCALE_JACOBI = 1 } rsp_cheby_scaling_t;
+typedef struct rsp_cheby *rsp_cheby_t;
+/* Host-blocking: plans A if needed, allocates dinv, d and w, runs the set-up.
+ * *position (may be NULL) = -1, or the row ZERO_PIVOT reports. A's values and
+ * pattern must not change while c lives; c must outlive every solver made on
+ * it and serves one solve at a time (its work vectors are its own).
+ * INVALID_VALUE: a NULL argument, a non-square A or one with no rows, a degree
+ * outside [1, RSP_CHEBY_MAX_DEGREE], a scaling outside the enum, a ratio that
+ * is not finite or <= 1, a bound that is not finite or <= 0. ZERO_PIVOT (JACOBI
+ * only): the smallest row whose diagonal is missing, 0 or not finite. */
+rsp_status_t rsp_cheby_create(rsp_handle_t handle, rsp_spmat_t A, int degree, rsp_cheby_scaling_t scaling,
+                              double ratio, int *position /* may be NULL */, rsp_cheby_t *c);
+rsp_status_t rsp_cheby_get_bounds(rsp_cheby_t c, double *lmin, double *lmax);
+/* Recomputes the coefficients (host only; an apply already enqueued keeps the
+ * old ones). INVALID_VALUE unless 0 < lmin < lmax and both are finite. */
+rsp_status_t rsp_cheby_set_bounds(rsp_cheby_t c, double lmin, double lmax);
+/* z = M^-1 r on the handle's stream, not host-blocking; d_r, d_z: n elements
+ * of P, naturally aligned (16-byte aligned ones move whole groups). Under
+ * rsp_set_ftz(1) an fp32 polynomial runs the flushing kernels.
+ * INVALID_VALUE: a NULL argument, d_r == d_z. */
+rsp_status_t rsp_cheby_apply(rsp_handle_t handle, rsp_cheby_t c, const void *d_r, void *d_z);
+rsp_status_t rsp_cheby_destroy(rsp_cheby_t c);
+/* Tests (no device needed): c0, a[degree - 1], b[degree - 1] (a[j-1] = a_j) in
+ * fp64, before the rounding to P. INVALID_VALUE: the degree or the bounds as
+ * above, a NULL c0, with degree > 1 a NULL a or b. */
+rsp_status_t rsp_cheby_coefficients_host(int degree, double lmin, double lmax, double *c0, double *a, double *b);
+/* The solvers on M = the polynomial c: as rsp_<solver>_create with c in the
+ * place of info, precond_type and d_factor; solve, history and destroy are
+ * unchanged. c's matrix may be A itself or a narrower descriptor over the same
+ * pattern (an fp32 polynomial under an fp64 iteration: its fp32 result is
+ * widened, as the fp32 ILU(0) apply's). INVALID_VALUE also for: a NULL c, P
+ * wider than A's type, c's n != rows; rsp_refine_create_cheby: a c that is not
+ * built on an fp32 matrix (normally A_low). */
+rsp_status_t rsp_bicgstab_create_cheby(rsp_handle_t handle, rsp_spmat_t A, rsp_cheby_t c, rsp_bicgstab_t *s);
+rsp_status_t rsp_cg_create_cheby(rsp_handle_t handle, rsp_spmat_t A, rsp_cheby_t c, rsp_cg_t *s);
+rsp_status_t rsp_gmres_create_cheby(rsp_handle_t handle, rsp_spmat_t A, rsp_cheby_t c, int restart,
+                                    rsp_gmres_t *s);
+rsp_status_t rsp_refine_create_cheby(rsp_handle_t handle, rsp_spmat_t A, rsp_spmat_t A_low, rsp_cheby_t c,
+                                     rsp_refine_method_t method, int restart, rsp_refine_t *s);
+
 /* ------------------------------------------------ multi-GPU halo exchange */
 
 /* Indexed gather dst[i] = src[idx[i]] for i < n (value_type elements). The

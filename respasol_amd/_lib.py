@@ -64,6 +64,9 @@ REFINE_GMRES = 2
 KRY_CHUNK = 2048
 KRY_MAX_GRID = 1024
 GMRES_MAX_RESTART = 64  # RSP_GMRES_MAX_RESTART
+CHEBY_MAX_DEGREE = 64  # RSP_CHEBY_MAX_DEGREE
+CHEBY_SCALE_NONE = 0
+CHEBY_SCALE_JACOBI = 1
 ILU_PLAN_FACTS = 104 # RSP_ILU_PLAN_FACTS
 
 MM_FULL_SYMMETRIC = 0x1
@@ -145,6 +148,17 @@ RSP_PROTOS = {
     "rsp_refine_destroy": (i32, [vp]),
     "rsp_convert_scaled": (i32, [vp, i64, i32, vp, i32, i32, vp]),
     "rsp_refine_update": (i32, [vp, i64, vp, i32, vp, vp]),
+    "rsp_cheby_create": (i32, [vp, vp, i32, i32, C.c_double, ip, C.POINTER(vp)]),
+    "rsp_cheby_get_bounds": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rsp_cheby_set_bounds": (i32, [vp, C.c_double, C.c_double]),
+    "rsp_cheby_apply": (i32, [vp, vp, vp, vp]),
+    "rsp_cheby_destroy": (i32, [vp]),
+    "rsp_cheby_coefficients_host": (i32, [i32, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rsp_bicgstab_create_cheby": (i32, [vp, vp, vp, C.POINTER(vp)]),
+    "rsp_cg_create_cheby": (i32, [vp, vp, vp, C.POINTER(vp)]),
+    "rsp_gmres_create_cheby": (i32, [vp, vp, vp, i32, C.POINTER(vp)]),
+    "rsp_refine_create_cheby": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(vp)]),
     "rsp_gather": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_scatter": (i32, [vp, i32, i64, vp, vp, vp]),
     "rsp_spmat_set_local_cols": (i32, [vp, i64]),

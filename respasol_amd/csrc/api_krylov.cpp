@@ -1,5 +1,6 @@
-// api_krylov.cpp — the Krylov solvers of include/rsp.h: ILU(0)-preconditioned
-// BiCGStab, preconditioned CG and restarted flexible GMRES(m), and the building
+// api_krylov.cpp — the Krylov solvers of include/rsp.h: BiCGStab, CG and
+// restarted flexible GMRES(m) preconditioned by ILU(0) or by the Chebyshev
+// polynomial of api_cheby.cpp (the *_create_cheby calls), and the building
 // blocks they expose (rsp_dot, rsp_orthogonalize, rsp_gmres_lsq_host), and
 // mixed-precision iterative refinement over them (rsp_refine_*,
 // rsp_convert_scaled, rsp_refine_update). Host
@@ -12,12 +13,14 @@ using namespace rsp_api;
 
 /* ------------------------------------------------- what both solvers share */
 
-// The operator, the preconditioner M = L U (info null: M = I) and its apply's
-// buffers, the device block and the pinned mirror the checks land in.
+// The operator, the preconditioner (M = L U of info, or the polynomial cheby;
+// both null: M = I) and its apply's buffers, the device block and the pinned
+// mirror the checks land in.
 struct KrylovCommon {
     int device = 0;
     rsp_spmat_t A = nullptr;
-    rsp_ilu0_info_t info = nullptr;  // null: M = I
+    rsp_ilu0_info_t info = nullptr;  // M = L U
+    rsp_cheby_t cheby = nullptr;     // M^-1 = the polynomial (never with info); both null: M = I
     rsp_datatype_t T = RSP_R_64F, P = RSP_R_64F;
     const void *factor = nullptr;
     long long n = 0;
@@ -28,7 +31,8 @@ struct KrylovCommon {
     hipEvent_t ev = nullptr;
     std::vector<double> history;
     int gen0[2] = {0, 0};  // the L and U solves' generations when the running solve call began
-    bool mixed() const { return info && P != T; }
+    bool precond() const { return info || cheby; }
+    bool mixed() const { return precond() && P != T; }
     int kry_type() const { return T == RSP_R_32F ? rsp::kKryF32 : (mixed() ? rsp::kKryF64Copy32 : rsp::kKryF64); }
     size_t tbytes() const { return align256((size_t)n * elem_size(T)); }  // one type-T vector in the arena
     ~KrylovCommon() {
@@ -50,8 +54,10 @@ static const void *zero_of(rsp_datatype_t t) { return t == RSP_R_64F ? (const vo
 // What both solvers' create calls check and finish before they allocate: the
 // arguments, A's schedule, the L and U solve plans, the factor's zero pivot.
 static rsp_status_t krylov_create_checks(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
-                                         rsp_datatype_t precond_type, const void *d_factor) {
+                                         rsp_datatype_t precond_type, const void *d_factor, rsp_cheby_t cheby) {
     if (!A || A->rows != A->cols || A->rows < 1) return RSP_STATUS_INVALID_VALUE;
+    if (cheby && (cheby->n != A->rows || (A->type == RSP_R_32F && cheby->P == RSP_R_64F)))
+        return RSP_STATUS_INVALID_VALUE;
     if (info) {
         if (precond_type != RSP_R_64F && precond_type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
         if (!info->analysed || info->n != A->rows || !d_factor) return RSP_STATUS_INVALID_VALUE;
@@ -69,24 +75,27 @@ static rsp_status_t krylov_create_checks(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0
 
 // The checked arguments into a new solver.
 static void krylov_bind(KrylovCommon &s, rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
-                        rsp_datatype_t precond_type, const void *d_factor) {
+                        rsp_datatype_t precond_type, const void *d_factor, rsp_cheby_t cheby) {
     s.device = h->device;
     s.A = A;
     s.info = info;
+    s.cheby = cheby;
     s.T = A->type;
-    s.P = info ? precond_type : A->type;
+    s.P = cheby ? cheby->P : (info ? precond_type : A->type);
     s.factor = d_factor;
     s.n = A->rows;
 }
 
 // The solver's one allocation: the device block of `blk` bytes, `tvec_bytes`
 // of type-T vectors (returned in *tvecs for the solver to lay out) and, at the
-// tail, the apply's type-P vectors (with M: pmid; mixed: pin, pmid, pout).
+// tail, the apply's type-P vectors (with M = L U: pmid; mixed: pin, pmid, pout;
+// the polynomial has its own work vectors: mixed only, pin and pout).
 // Then the pinned mirror of `mirror_doubles` and the event of the checks.
 static rsp_status_t krylov_alloc(KrylovCommon &s, size_t blk, size_t tvec_bytes, size_t mirror_doubles,
                                  char **tvecs) {
     const size_t pb = align256((size_t)s.n * elem_size(s.P));
-    const int np = !s.info ? 0 : (s.mixed() ? 3 : 1);
+    const int nmid = s.info ? 1 : 0;
+    const int np = s.mixed() ? 2 + nmid : nmid;
     RSP_CHECK_HIP(hipMalloc(&s.d_arena, blk + tvec_bytes + np * pb));
     char *at = (char *)s.d_arena;
     s.d_blk = (double *)at;
@@ -94,8 +103,8 @@ static rsp_status_t krylov_alloc(KrylovCommon &s, size_t blk, size_t tvec_bytes,
     at += blk + tvec_bytes;
     if (s.mixed()) {
         s.pin = at;
-        s.pmid = at + pb;
-        s.pout = at + 2 * pb;
+        s.pmid = nmid ? at + pb : nullptr;
+        s.pout = at + (1 + nmid) * pb;
     } else if (s.info) {
         s.pmid = at;
     }
@@ -108,15 +117,19 @@ static rsp_status_t krylov_spmv(rsp_handle_t h, const KrylovCommon &s, const voi
     return spmv_run(h, RSP_OPERATION_NON_TRANSPOSE, one_of(s.T), s.A, x, zero_of(s.T), y, s.T, nullptr, 0);
 }
 
-// z = M^-1 y with M = L U: y -> L -> pmid -> U -> z; in mixed mode y's fp32
-// copy (written by the kernel that made y) is the input and the fp32 result
-// is widened into z for the fp64 SpMV.
+// z = M^-1 y with M = L U: y -> L -> pmid -> U -> z, or the polynomial's apply;
+// in mixed mode y's fp32 copy (written by the kernel that made y) is the input
+// and the fp32 result is widened into z for the fp64 SpMV.
 static rsp_status_t krylov_apply(rsp_handle_t h, const KrylovCommon &s, const void *y, void *z, bool ftz) {
     const void *one = one_of(s.P);
     const void *in = s.mixed() ? s.pin : y;
     void *res = s.mixed() ? s.pout : z;
-    RSP_TRY(rsp_trsv_lower_unit_impl(h, RSP_OPERATION_NON_TRANSPOSE, one, s.info, s.P, s.factor, in, s.pmid, true));
-    RSP_TRY(rsp_trsv_upper_impl(h, one, s.info, s.P, s.factor, s.pmid, res, true));
+    if (s.cheby) {
+        RSP_TRY(cheby_apply(h, s.cheby, in, res));
+    } else {
+        RSP_TRY(rsp_trsv_lower_unit_impl(h, RSP_OPERATION_NON_TRANSPOSE, one, s.info, s.P, s.factor, in, s.pmid, true));
+        RSP_TRY(rsp_trsv_upper_impl(h, one, s.info, s.P, s.factor, s.pmid, res, true));
+    }
     if (!s.mixed()) return RSP_STATUS_SUCCESS;
     rsp::KryArgs a{};
     a.n = s.n;
@@ -148,7 +161,7 @@ static rsp_status_t krylov_solve_begin(rsp_handle_t h, KrylovCommon *s, const vo
 // call (of `iters` iterations) at once: a flow launch that gave up a wait left
 // its generation in the solve's status word. The solver's buffers are reused
 // every iteration, so the recovery of rsp_trsv_zero_pivot (re-running the
-// recorded solves) cannot apply: reported.
+// recorded solves) cannot apply: reported. (A polynomial has nothing to read.)
 static rsp_status_t krylov_solve_end(rsp_handle_t h, const KrylovCommon &s, int iters) {
     if (!s.info || iters <= 0) return RSP_STATUS_SUCCESS;
     int z[5];
@@ -176,22 +189,23 @@ struct rsp_bicgstab : KrylovCommon {
 };
 
 static rsp_status_t bicgstab_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
-                                    rsp_datatype_t precond_type, const void *d_factor, rsp_bicgstab_t *out) {
+                                    rsp_datatype_t precond_type, const void *d_factor, rsp_cheby_t cheby,
+                                    rsp_bicgstab_t *out) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!out) return RSP_STATUS_INVALID_VALUE;
     *out = nullptr;
-    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor));
+    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor, cheby));
     std::unique_ptr<rsp_bicgstab> s(new rsp_bicgstab);  // (a half-built solver is freed on every way out)
-    krylov_bind(*s, h, A, info, precond_type, d_factor);
+    krylov_bind(*s, h, A, info, precond_type, d_factor, cheby);
     // r, rhat, p, v, s, t; with M: phat, shat (T) and the apply's vectors (P)
     const size_t tb = s->tbytes();
-    const int nt = info ? 8 : 6;
+    const int nt = s->precond() ? 8 : 6;
     char *at = nullptr;
     RSP_TRY(krylov_alloc(*s, align256(rsp::kKryBlockDoubles * sizeof(double)), nt * tb,
                          rsp::kKryScalars + 2 * (size_t)rsp::kKryMaxGrid, &at));
     void **tv[] = {&s->r, &s->rhat, &s->p, &s->v, &s->s, &s->t, &s->phat, &s->shat};
     for (int k = 0; k < nt; k++, at += tb) *tv[k] = at;
-    if (!info) {
+    if (!s->precond()) {
         s->phat = s->p;
         s->shat = s->s;
     }
@@ -265,11 +279,11 @@ static rsp_status_t bicgstab_solve(rsp_handle_t h, rsp_bicgstab_t s, const void 
         for (int it = 1; it <= max_iters; it++) {
             a.it = it;
             RSP_TRY(kern(rsp::kKryPUpdate));
-            if (s->info) RSP_TRY(krylov_apply(h, *s, s->p, s->phat, ftz));
+            if (s->precond()) RSP_TRY(krylov_apply(h, *s, s->p, s->phat, ftz));
             RSP_TRY(krylov_spmv(h, *s, s->phat, s->v));
             RSP_TRY(kern(rsp::kKryDotRhV));
             RSP_TRY(kern(rsp::kKrySUpdate));
-            if (s->info) RSP_TRY(krylov_apply(h, *s, s->s, s->shat, ftz));
+            if (s->precond()) RSP_TRY(krylov_apply(h, *s, s->s, s->shat, ftz));
             RSP_TRY(krylov_spmv(h, *s, s->shat, s->t));
             RSP_TRY(kern(rsp::kKryDotTS));
             RSP_TRY(kern(rsp::kKryXUpdate));
@@ -333,21 +347,21 @@ struct rsp_cg : KrylovCommon {
 };
 
 static rsp_status_t cg_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
-                              const void *d_factor, rsp_cg_t *out) {
+                              const void *d_factor, rsp_cheby_t cheby, rsp_cg_t *out) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!out) return RSP_STATUS_INVALID_VALUE;
     *out = nullptr;
-    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor));
+    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor, cheby));
     std::unique_ptr<rsp_cg> s(new rsp_cg);  // (a half-built solver is freed on every way out)
-    krylov_bind(*s, h, A, info, precond_type, d_factor);
+    krylov_bind(*s, h, A, info, precond_type, d_factor, cheby);
     const size_t tb = s->tbytes();
-    const int nt = info ? 4 : 3;
+    const int nt = s->precond() ? 4 : 3;
     char *at = nullptr;
     RSP_TRY(krylov_alloc(*s, align256(rsp::kKryBlockDoubles * sizeof(double)), nt * tb,
                          rsp::kKryScalars + 2 * (size_t)rsp::kKryMaxGrid, &at));
     void **tv[] = {&s->r, &s->p, &s->q, &s->z};
     for (int k = 0; k < nt; k++, at += tb) *tv[k] = at;
-    if (!info) s->z = s->r;
+    if (!s->precond()) s->z = s->r;
     *out = s.release();
     return RSP_STATUS_SUCCESS;
 }
@@ -411,7 +425,7 @@ static rsp_status_t cg_solve(rsp_handle_t h, rsp_cg_t s, const void *d_b, void *
     } else {
         for (int it = 1; it <= max_iters; it++) {
             a.it = it;
-            if (s->info) {
+            if (s->precond()) {
                 RSP_TRY(krylov_apply(h, *s, s->r, s->z, ftz));
                 RSP_TRY(kern(rsp::kKryCgDotRZ));
             }
@@ -455,19 +469,19 @@ struct rsp_gmres : KrylovCommon {
 };
 
 static rsp_status_t gmres_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
-                                 const void *d_factor, int restart, rsp_gmres_t *out) {
+                                 const void *d_factor, rsp_cheby_t cheby, int restart, rsp_gmres_t *out) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!out) return RSP_STATUS_INVALID_VALUE;
     *out = nullptr;
     if (restart < 1 || restart > RSP_GMRES_MAX_RESTART) return RSP_STATUS_INVALID_VALUE;
-    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor));
+    RSP_TRY(krylov_create_checks(h, A, info, precond_type, d_factor, cheby));
     std::unique_ptr<rsp_gmres> s(new rsp_gmres);  // (a half-built solver is freed on every way out)
-    krylov_bind(*s, h, A, info, precond_type, d_factor);
+    krylov_bind(*s, h, A, info, precond_type, d_factor, cheby);
     s->m = restart;
     const size_t tb = s->tbytes();
     s->ld = (long long)(tb / elem_size(s->T));
     // V (m + 1), w; with M: Z (m) and the apply's vectors (P)
-    const size_t nt = (size_t)s->m + 2 + (info ? s->m : 0);
+    const size_t nt = (size_t)s->m + 2 + (s->precond() ? s->m : 0);
     char *at = nullptr;
     RSP_TRY(krylov_alloc(*s, align256(rsp::kGmBlockDoubles * sizeof(double)), nt * tb,
                          rsp::kGmHead + 2 * (size_t)rsp::kKryMaxGrid, &at));
@@ -475,7 +489,7 @@ static rsp_status_t gmres_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t 
     at += ((size_t)s->m + 1) * tb;
     s->w = at;
     at += tb;
-    s->Z = info ? at : s->V;
+    s->Z = s->precond() ? at : s->V;
     *out = s.release();
     return RSP_STATUS_SUCCESS;
 }
@@ -560,7 +574,7 @@ static rsp_status_t gmres_solve(rsp_handle_t h, rsp_gmres_t s, const void *d_b, 
             while (cols < s->m && total + cols < max_iters) {
                 const int j = cols;
                 // z_j = M^-1 v_j (mixed: from v_j's fp32 copy, written by the kernel that made v_j)
-                if (s->info) RSP_TRY(krylov_apply(h, *s, s->V + (size_t)j * tb, s->Z + (size_t)j * tb, ftz));
+                if (s->precond()) RSP_TRY(krylov_apply(h, *s, s->V + (size_t)j * tb, s->Z + (size_t)j * tb, ftz));
                 RSP_TRY(krylov_spmv(h, *s, s->Z + (size_t)j * tb, s->w));
                 RSP_TRY(kern(rsp::kGmMultiDot, j, 0));
                 RSP_TRY(kern(rsp::kGmUpdate1, j, 0));
@@ -710,13 +724,14 @@ struct rsp_refine : KrylovCommon {
 };
 
 static rsp_status_t refine_create(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_low, rsp_ilu0_info_t info,
-                                  const void *d_factor_low, rsp_refine_method_t method, int restart,
-                                  rsp_refine_t *out) {
+                                  const void *d_factor_low, rsp_cheby_t cheby, rsp_refine_method_t method,
+                                  int restart, rsp_refine_t *out) {
     if (!h) return RSP_STATUS_NOT_INITIALIZED;
     if (!out) return RSP_STATUS_INVALID_VALUE;
     *out = nullptr;
     if (!A || !A_low || (info && !d_factor_low)) return RSP_STATUS_INVALID_VALUE;
     if (A->type != RSP_R_64F || A_low->type != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
+    if (cheby && cheby->P != RSP_R_32F) return RSP_STATUS_INVALID_VALUE;
     if (A->rows != A->cols || A->rows < 1 || A_low->rows != A->rows || A_low->cols != A->cols)
         return RSP_STATUS_INVALID_VALUE;
     if (method != RSP_REFINE_BICGSTAB && method != RSP_REFINE_CG && method != RSP_REFINE_GMRES)
@@ -725,17 +740,20 @@ static rsp_status_t refine_create(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_l
         return RSP_STATUS_INVALID_VALUE;
     if (!A->planned || A->plan_type != A->type) RSP_TRY(spmv_plan(h, A, A->type));
     std::unique_ptr<rsp_refine> s(new rsp_refine);  // (a half-built one is freed on every way out, its inner solver too)
-    krylov_bind(*s, h, A, nullptr, RSP_R_64F, nullptr);
+    krylov_bind(*s, h, A, nullptr, RSP_R_64F, nullptr, nullptr);
     s->method = method;
     switch (method) {
         case RSP_REFINE_BICGSTAB:
-            RSP_TRY(rsp_bicgstab_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->bicgstab));
+            RSP_TRY(cheby ? rsp_bicgstab_create_cheby(h, A_low, cheby, &s->bicgstab)
+                          : rsp_bicgstab_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->bicgstab));
             break;
         case RSP_REFINE_CG:
-            RSP_TRY(rsp_cg_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->cg));
+            RSP_TRY(cheby ? rsp_cg_create_cheby(h, A_low, cheby, &s->cg)
+                          : rsp_cg_create(h, A_low, info, RSP_R_32F, d_factor_low, &s->cg));
             break;
         default:
-            RSP_TRY(rsp_gmres_create(h, A_low, info, RSP_R_32F, d_factor_low, restart, &s->gmres));
+            RSP_TRY(cheby ? rsp_gmres_create_cheby(h, A_low, cheby, restart, &s->gmres)
+                          : rsp_gmres_create(h, A_low, info, RSP_R_32F, d_factor_low, restart, &s->gmres));
             break;
     }
     // r, v, x_old (fp64), then r32, d (fp32)
@@ -887,7 +905,18 @@ extern "C" {
 
 rsp_status_t rsp_refine_create(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_low, rsp_ilu0_info_t info,
                                const void *d_factor_low, rsp_refine_method_t method, int restart, rsp_refine_t *s) {
-    return guarded([&] { return refine_create(h, A, A_low, info, d_factor_low, method, restart, s); });
+    return guarded([&] { return refine_create(h, A, A_low, info, d_factor_low, nullptr, method, restart, s); });
+}
+
+rsp_status_t rsp_refine_create_cheby(rsp_handle_t h, rsp_spmat_t A, rsp_spmat_t A_low, rsp_cheby_t c,
+                                     rsp_refine_method_t method, int restart, rsp_refine_t *s) {
+    return guarded([&] {
+        if (h && s && !c) {
+            *s = nullptr;
+            return RSP_STATUS_INVALID_VALUE;
+        }
+        return refine_create(h, A, A_low, nullptr, nullptr, c, method, restart, s);
+    });
 }
 
 rsp_status_t rsp_refine_solve(rsp_handle_t h, rsp_refine_t s, const void *d_b, void *d_x, double rtol, int max_steps,
@@ -920,7 +949,17 @@ rsp_status_t rsp_refine_update(rsp_handle_t h, int64_t n, const float *d_d, int 
 
 rsp_status_t rsp_bicgstab_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info,
                                  rsp_datatype_t precond_type, const void *d_factor, rsp_bicgstab_t *s) {
-    return guarded([&] { return bicgstab_create(h, A, info, precond_type, d_factor, s); });
+    return guarded([&] { return bicgstab_create(h, A, info, precond_type, d_factor, nullptr, s); });
+}
+
+rsp_status_t rsp_bicgstab_create_cheby(rsp_handle_t h, rsp_spmat_t A, rsp_cheby_t c, rsp_bicgstab_t *s) {
+    return guarded([&] {
+        if (h && s && !c) {
+            *s = nullptr;
+            return RSP_STATUS_INVALID_VALUE;
+        }
+        return bicgstab_create(h, A, nullptr, RSP_R_64F, nullptr, c, s);
+    });
 }
 
 rsp_status_t rsp_bicgstab_solve(rsp_handle_t h, rsp_bicgstab_t s, const void *d_b, void *d_x, double rtol,
@@ -946,7 +985,17 @@ rsp_status_t rsp_dot(rsp_handle_t h, rsp_datatype_t value_type, int64_t n, const
 
 rsp_status_t rsp_cg_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
                            const void *d_factor, rsp_cg_t *s) {
-    return guarded([&] { return cg_create(h, A, info, precond_type, d_factor, s); });
+    return guarded([&] { return cg_create(h, A, info, precond_type, d_factor, nullptr, s); });
+}
+
+rsp_status_t rsp_cg_create_cheby(rsp_handle_t h, rsp_spmat_t A, rsp_cheby_t c, rsp_cg_t *s) {
+    return guarded([&] {
+        if (h && s && !c) {
+            *s = nullptr;
+            return RSP_STATUS_INVALID_VALUE;
+        }
+        return cg_create(h, A, nullptr, RSP_R_64F, nullptr, c, s);
+    });
 }
 
 rsp_status_t rsp_cg_solve(rsp_handle_t h, rsp_cg_t s, const void *d_b, void *d_x, double rtol, int max_iters,
@@ -966,7 +1015,17 @@ rsp_status_t rsp_cg_destroy(rsp_cg_t s) {
 
 rsp_status_t rsp_gmres_create(rsp_handle_t h, rsp_spmat_t A, rsp_ilu0_info_t info, rsp_datatype_t precond_type,
                               const void *d_factor, int restart, rsp_gmres_t *s) {
-    return guarded([&] { return gmres_create(h, A, info, precond_type, d_factor, restart, s); });
+    return guarded([&] { return gmres_create(h, A, info, precond_type, d_factor, nullptr, restart, s); });
+}
+
+rsp_status_t rsp_gmres_create_cheby(rsp_handle_t h, rsp_spmat_t A, rsp_cheby_t c, int restart, rsp_gmres_t *s) {
+    return guarded([&] {
+        if (h && s && !c) {
+            *s = nullptr;
+            return RSP_STATUS_INVALID_VALUE;
+        }
+        return gmres_create(h, A, nullptr, RSP_R_64F, nullptr, c, restart, s);
+    });
 }
 
 rsp_status_t rsp_gmres_solve(rsp_handle_t h, rsp_gmres_t s, const void *d_b, void *d_x, double rtol, int max_iters,

@@ -46,45 +46,13 @@
 #define RSP_KNS rsp_k
 #endif
 
+#include "kry_vec.h"  // Grp, ld, st, KRY_FOR_GROUPS, aligned16 (shared with cheby.hip)
+
 namespace RSP_KNS {
 
 using namespace rsp;
 
 namespace {
-
-template <typename T>
-struct Grp {
-    static constexpr int V = 16 / sizeof(T);
-    T e[V];
-};
-
-template <typename T, bool VEC>
-__device__ __forceinline__ Grp<T> ld(const T *p, long long j, int cnt) {
-    Grp<T> g;
-    if (VEC && cnt == Grp<T>::V) {
-        using V4 = __attribute__((ext_vector_type(4))) unsigned;
-        const V4 w = *reinterpret_cast<const V4 *>(p + j);
-        __builtin_memcpy(g.e, &w, 16);
-    } else {
-#pragma unroll
-        for (int k = 0; k < Grp<T>::V; k++) g.e[k] = k < cnt ? p[j + k] : T(0);
-    }
-    return g;
-}
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void st(T *p, long long j, int cnt, const Grp<T> &g) {
-    if (VEC && cnt == Grp<T>::V) {
-        using V4 = __attribute__((ext_vector_type(4))) unsigned;
-        V4 w;
-        __builtin_memcpy(&w, g.e, 16);
-        *reinterpret_cast<V4 *>(p + j) = w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < Grp<T>::V; k++)
-            if (k < cnt) p[j + k] = g.e[k];
-    }
-}
 
 // the fp32 copy of a double group (own allocation: 8-byte aligned at even j)
 template <bool VEC>
@@ -137,14 +105,6 @@ __device__ __forceinline__ void set_break(double *blk, int code, int it) {
         blk[kKryFlagIt] = (double)it;
     }
 }
-
-// the loop every kernel shares: thread t's groups of the workgroup's range
-#define KRY_FOR_GROUPS(T, n, chunk)                                                             \
-    const long long c0_ = (long long)blockIdx.x * (chunk);                                      \
-    const long long c1_ = c0_ + (chunk) < (n) ? c0_ + (chunk) : (n);                            \
-    for (long long j = c0_ + (long long)threadIdx.x * Grp<T>::V; j < c1_;                       \
-         j += (long long)kKryThreads * Grp<T>::V)                                               \
-        if (const int cnt = (int)(c1_ - j < Grp<T>::V ? c1_ - j : Grp<T>::V))
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kKryThreads) void kry_init(long long n, long long chunk, double *blk,
@@ -980,12 +940,6 @@ __global__ __launch_bounds__(kKryThreads) void ref_update(long long n, long long
         for (int k = 0; k < 4; k++) xx[k] = xx[k] + scale * dd[k];
         ref_st4<double, VEC>(x, j, cnt, xx);
     }
-}
-
-inline bool aligned16(std::initializer_list<const void *> ps) {
-    uintptr_t m = 0;
-    for (const void *p : ps) m |= (uintptr_t)p;
-    return (m & 15) == 0;
 }
 
 template <typename T, bool COPY>

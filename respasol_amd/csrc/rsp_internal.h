@@ -8,6 +8,7 @@
 //   api_ilu_analysis.cpp  ILU(0) analysis, the solve plans, the plan queries
 //   api_ilu_solve.cpp     factor and triangular solves, flow give-up recovery
 //   api_krylov.cpp        BiCGStab, CG, GMRES, rsp_dot, rsp_orthogonalize, iterative refinement
+//   api_cheby.cpp         the Chebyshev polynomial preconditioner
 #pragma once
 
 #include "rsp.h"
@@ -229,7 +230,29 @@ struct rsp_ilu0_info {
     }
 };
 
-#define RSP_CHECK_HIP(call)                                                     \
+// A Chebyshev polynomial preconditioner (api_cheby.cpp; include/rsp.h): the
+// matrix it is built on (of type P), the bounds, the coefficients rounded to P
+// and one allocation holding dinv (JACOBI only) and the work vectors d and w.
+struct rsp_cheby {
+    int device = 0;
+    rsp_spmat_t A = nullptr;
+    rsp_datatype_t P = RSP_R_64F;
+    long long n = 0;
+    int degree = 1;
+    double lmin = 0.0, lmax = 0.0;
+    double c0 = 0.0, a[RSP_CHEBY_MAX_DEGREE] = {}, b[RSP_CHEBY_MAX_DEGREE] = {};  // values of P; a[j], b[j]: term j
+    void *d_mem = nullptr;
+    void *dinv = nullptr, *d = nullptr, *w = nullptr;  // dinv null: RSP_CHEBY_SCALE_NONE
+    ~rsp_cheby() {
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        (void)hipSetDevice(device);
+        if (d_mem) (void)hipFree(d_mem);
+        (void)hipSetDevice(cur);
+    }
+};
+
+#define RSP_CHECK_HIP(call)                                                    \
     do {                                                                        \
         hipError_t e_ = (call);                                                 \
         if (e_ != hipSuccess)                                                   \
@@ -292,5 +315,9 @@ rsp_status_t rsp_trsv_lower_unit_impl(rsp_handle_t h, rsp_operation_t op, const 
                                       bool flow_ok);
 rsp_status_t rsp_trsv_upper_impl(rsp_handle_t h, const void *alpha, rsp_ilu0_info *f, rsp_datatype_t value_type,
                                  const void *d_values, const void *d_x, void *d_y, bool flow_ok);
+
+// api_cheby.cpp
+// z = p_k(D^-1 A) D^-1 r on the handle's stream (rsp_cheby_apply without the guard).
+rsp_status_t cheby_apply(rsp_handle_t h, rsp_cheby *c, const void *d_r, void *d_z);
 
 }  // namespace rsp_api

@@ -610,6 +610,38 @@ struct RefArgs {
     double *x_old;         // kRefUpdate, may be null
 };
 
+// Chebyshev polynomial preconditioner (cheby.hip; rsp_cheby_*): z = p_k(D^-1 A)
+// D^-1 r as k element-wise kernels on the grid and chunks above, with one
+// rsp_spmv between two of them (w = w - A d, by its alpha / beta epilogue). P
+// is the type of the matrix the polynomial is built on; every product and sum
+// is rounded to P, so an element's result depends on its own inputs alone.
+enum ChebyOp {
+    kChebyFirst,  // d_i = c0 * (dinv_i * r_i); z_i = d_i; w_i = r_i   (only_z: z alone is written)
+    kChebyStep    // t = dinv_i * w_i; d_i = (a * d_i) + (b * t); z_i = z_i + d_i   (only_z: d is not stored)
+};
+struct ChebyArgs {
+    long long n;
+    double c0, a, b;   // the term's coefficients, already rounded to P
+    int only_z;        // kChebyFirst: degree 1; kChebyStep: the last term
+    const void *dinv;  // null: no scaling (the product with dinv is skipped)
+    const void *r;     // kChebyFirst
+    void *z, *d, *w;
+};
+// The set-up, one lane per row i: diag_i = the sum in P, in storage order, of
+// the stored entries of column i; dinv_i = P(1) / diag_i; g_i = (sum_j
+// |double(a_ij)| in fp64, storage order) / |double(diag_i)| (dinv null: / 1).
+// state[0] receives max_i g_i as the bits of a non-negative double (a g_i that
+// is not finite counts as +inf), state[1] the smallest row whose diagonal is
+// missing, 0 or not finite (dinv non-null only; such a row adds nothing to the
+// maximum); the caller presets them to 0 and ~0.
+struct ChebySetupArgs {
+    int n;
+    const int *rowptr, *colidx;
+    const void *vals;
+    void *dinv;  // may be null
+    unsigned long long *state;
+};
+
 // Restarted flexible GMRES (krylov.hip gm_* kernels, rsp_gmres_*,
 // rsp_orthogonalize): the same grid, chunks and partials as above. Its device
 // block, all fp64: a head of scalars and the estimates (what a mid-cycle check
@@ -733,6 +765,8 @@ RSP_HD inline int gmres_lsq(double *col, int j, double *cs, double *sn, double *
     hipError_t gmres(rsp::GmOp op, int type, const rsp::GmArgs &a, hipStream_t s);              \
     hipError_t refine(rsp::RefOp op, const rsp::RefArgs &a, hipStream_t s);                     \
     void warm_krylov();                                                                         \
+    hipError_t cheby(rsp::ChebyOp op, int f32, const rsp::ChebyArgs &a, hipStream_t s);         \
+    hipError_t cheby_setup(int f32, const rsp::ChebySetupArgs &a, hipStream_t s);               \
     }
 
 RSP_DECLARE_KERNEL_API(rsp_k)

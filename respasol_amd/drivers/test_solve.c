@@ -1,5 +1,5 @@
 /*
- * test_solve.c — ILU(0)-preconditioned BiCGStab / GMRES(m) / CG driver, with
+ * test_solve.c — ILU(0)- or Chebyshev-preconditioned BiCGStab / GMRES(m) / CG driver, with
  * --refine the same inside mixed-precision iterative refinement (built as
  * `test_solve`).
  * No GPU counterpart in the reference; shaped like its direct-solver drivers
@@ -9,7 +9,7 @@
  *   test_solve <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32]
  *              [--precond=fp64|fp32|none] [--ftz] [--rtol=R] [--maxit=N]
  *              [--full-symmetric] [--dump=FILE] [--method=bicgstab|gmres|cg]
- *              [--restart=M] [--refine[=inner_rtol]]
+ *              [--restart=M] [--refine[=inner_rtol]] [--cheby=K] [--cheby-ratio=R]
  *
  * Flow: load as test_ilu0 does (outputbase 0); iteration values in --prec;
  * b = 1, x0 = 0; [timed "Symbolic"] ILU analysis; [timed "Numeric"]
@@ -30,6 +30,12 @@
  * all-fp32 solves by --method to inner_rtol (default 1e-4), each of at most
  * --maxit iterations, at most 50 steps; "Iterations" is then the inner
  * iterations of all steps, and two more lines follow the report.
+ * --cheby=K (1..64; with --precond=none: exit 2): the preconditioner is the
+ * degree-K Chebyshev polynomial (rsp_cheby_create, Jacobi scaling, lmin = lmax
+ * / R, --cheby-ratio=R, default 30) in the --precond type instead of ILU(0) —
+ * on A itself, or on an fp32 descriptor of the same pattern when --precond is
+ * narrower than --prec; with --refine it is fp32. "Symbolic" is then the
+ * polynomial's set-up (wall-clock) and "Numeric" is 0.
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -75,7 +81,7 @@ int main(int argc, char **argv) {
                 "  %s <A.mtx | surrogate:NAME[@scale]> [--prec=fp64|fp32] [--precond=fp64|fp32|none]\n"
                 "     [--ftz] [--rtol=R] [--maxit=N] [--full-symmetric] [--dump=FILE]\n"
                 "     [--method=bicgstab|gmres|cg] [--restart=M]\n"
-                "     [--refine[=inner_rtol]]\n"
+                "     [--refine[=inner_rtol]] [--cheby=K] [--cheby-ratio=R]\n"
                 "  solves A x = 1 from x0 = 0 by ILU(0)-preconditioned BiCGStab.\n"
                 "  --method=gmres: by restarted flexible GMRES(M) instead (--restart, default 30).\n"
                 "  --method=cg: by preconditioned conjugate gradients (A symmetric positive definite).\n"
@@ -83,7 +89,9 @@ int main(int argc, char **argv) {
                 "  or --method=cg, which needs both triangles, is.\n"
                 "  --refine: mixed-precision iterative refinement, fp64 residuals around all-fp32\n"
                 "  solves by --method to inner_rtol (default 1e-4); needs --prec=fp64 and\n"
-                "  --precond=fp32 or none.\n",
+                "  --precond=fp32 or none.\n"
+                "  --cheby=K: the degree-K Chebyshev polynomial preconditioner in the --precond type\n"
+                "  instead of ILU(0), on [lmax / R, lmax] (--cheby-ratio=R, default 30).\n",
                 argv[0]);
         return 2;
     }
@@ -100,6 +108,11 @@ int main(int argc, char **argv) {
     const char *refine_s = drv_flag(argc, argv, 2, "refine");
     const int refine = refine_s != NULL;
     const double inner_rtol = refine_s && *refine_s ? atof(refine_s) : 1e-4;
+    const char *cheby_s = drv_flag(argc, argv, 2, "cheby");
+    const char *ratio_s = drv_flag(argc, argv, 2, "cheby-ratio");
+    const int cheby = cheby_s != NULL;
+    const int cheby_degree = cheby_s && *cheby_s ? atoi(cheby_s) : 4;
+    const double cheby_ratio = ratio_s && *ratio_s ? atof(ratio_s) : 30.0;
     if (method && *method && !gmres && !cg && strcmp(method, "bicgstab") != 0) {
         fprintf(stderr, "Error: --method is bicgstab, gmres or cg\n");
         return 2;
@@ -113,6 +126,11 @@ int main(int argc, char **argv) {
     const int maxit = maxit_s && *maxit_s ? atoi(maxit_s) : 1000;
     if (use_m && fp32 && !m32) {
         fprintf(stderr, "Error: --precond=fp64 is wider than --prec=fp32\n");
+        return 2;
+    }
+
+    if (cheby && !use_m) {
+        fprintf(stderr, "Error: --cheby needs a preconditioner type: --precond=fp64 or fp32\n");
         return 2;
     }
 
@@ -172,7 +190,7 @@ int main(int argc, char **argv) {
     float time_symbolic = 0.0f, time_numeric = 0.0f, time_solve = 0.0f;
 
     rsp_ilu0_info_t info = NULL;
-    if (use_m) {
+    if (use_m && !cheby) {
         RSP_OR_FAIL(rsp_create_ilu0_info(&info));
         double t0 = drv_wtime();
         RSP_OR_FAIL(rsp_ilu0_analysis(handle, n, A.nnz, d_rp, d_ci, info));
@@ -196,13 +214,42 @@ int main(int argc, char **argv) {
     rsp_spmat_t mat_low = NULL;
     void *d_vlow = NULL;
     int steps = 0;
+    rsp_cheby_t poly = NULL;
+    rsp_spmat_t mat_poly = NULL; /* the polynomial's matrix when --precond is narrower than --prec */
     if (refine) {
         HIP_OR_FAIL(hipMalloc(&d_vlow, (size_t)(nnz_s ? nnz_s : 1) * sizeof(float)));
         RSP_OR_FAIL(rsp_convert_scaled(handle, nnz_s, RSP_R_64F, d_v, 0, RSP_R_32F, d_vlow));
         RSP_OR_FAIL(rsp_create_csr(&mat_low, n, n, A.nnz, d_rp, d_ci, d_vlow, RSP_R_32F));
-        RSP_OR_FAIL(rsp_refine_create(handle, mat, mat_low, info, d_m,
-                                      gmres ? RSP_REFINE_GMRES : (cg ? RSP_REFINE_CG : RSP_REFINE_BICGSTAB), restart,
-                                      &rsolver));
+    }
+    if (cheby) {
+        rsp_spmat_t on = refine ? mat_low : mat;
+        if (!refine && m32 != fp32) {
+            RSP_OR_FAIL(rsp_create_csr(&mat_poly, n, n, A.nnz, d_rp, d_ci, d_m, mt));
+            on = mat_poly;
+        }
+        int pos = -1;
+        double t0 = drv_wtime();
+        rsp_status_t st = rsp_cheby_create(handle, on, cheby_degree, RSP_CHEBY_SCALE_JACOBI, cheby_ratio, &pos, &poly);
+        time_symbolic = (float)((drv_wtime() - t0) * 1e3);
+        if (st == RSP_STATUS_ZERO_PIVOT) {
+            fprintf(stderr, "Error: A(%d,%d) is missing or zero\n", pos, pos);
+            return 1;
+        }
+        RSP_OR_FAIL(st);
+    }
+    if (refine) {
+        const rsp_refine_method_t rm = gmres ? RSP_REFINE_GMRES : (cg ? RSP_REFINE_CG : RSP_REFINE_BICGSTAB);
+        if (cheby)
+            RSP_OR_FAIL(rsp_refine_create_cheby(handle, mat, mat_low, poly, rm, restart, &rsolver));
+        else
+            RSP_OR_FAIL(rsp_refine_create(handle, mat, mat_low, info, d_m, rm, restart, &rsolver));
+    } else if (cheby) {
+        if (gmres)
+            RSP_OR_FAIL(rsp_gmres_create_cheby(handle, mat, poly, restart, &gsolver));
+        else if (cg)
+            RSP_OR_FAIL(rsp_cg_create_cheby(handle, mat, poly, &csolver));
+        else
+            RSP_OR_FAIL(rsp_bicgstab_create_cheby(handle, mat, poly, &solver));
     } else if (gmres)
         RSP_OR_FAIL(rsp_gmres_create(handle, mat, info, mt, d_m, restart, &gsolver));
     else if (cg)
@@ -264,6 +311,8 @@ int main(int argc, char **argv) {
     else
         rsp_bicgstab_destroy(solver);
     if (info) rsp_destroy_ilu0_info(info);
+    if (poly) rsp_cheby_destroy(poly);
+    if (mat_poly) rsp_destroy_spmat(mat_poly);
     rsp_destroy_spmat(mat);
     rsp_destroy(handle);
     hipFree(d_rp);

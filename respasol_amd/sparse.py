@@ -32,6 +32,11 @@ Mapping to the reference's cuSPARSE usage:
   Refine                 mixed-precision iterative refinement: fp64 residuals
                          and updates around an all-fp32 BiCGStab / CG / GMRES
                          solve of the correction (rsp_refine_*)
+  Cheby                  a Chebyshev polynomial preconditioner z = p_k(D^-1 A)
+                         D^-1 r made of SpMVs alone (rsp_cheby_*); the solvers
+                         take it as cheby= in the place of ilu= / factor=
+  cheby_coefficients     its coefficients in fp64, no device
+                         (rsp_cheby_coefficients_host)
   convert_scaled         dst = dst_type(src * 2^exp2), one rounding
                          (rsp_convert_scaled)
   refine_update          x_old = x; x += 2^exp2 * double(d) (rsp_refine_update)
@@ -421,6 +426,85 @@ class Ilu0:
             pass
 
 
+class Cheby:
+    """A Chebyshev polynomial preconditioner on A (rsp_cheby_*): z = p_k(D^-1 A)
+    D^-1 r with `degree` terms (degree - 1 SpMVs per apply), D the diagonal
+    (scaling="jacobi") or I ("none"), on [lmax / ratio, lmax], lmax the
+    Gershgorin bound of D^-1 A. A's dtype is the polynomial's type. A missing,
+    zero or non-finite diagonal raises RspError(ZERO_PIVOT) whose `position` is
+    the smallest such row. A is kept alive; one Cheby serves one solve at a time."""
+
+    SCALINGS = {"none": _lib.CHEBY_SCALE_NONE, "jacobi": _lib.CHEBY_SCALE_JACOBI}
+
+    def __init__(self, handle: Handle, A: SpMat, degree: int = 4, scaling: str = "jacobi", ratio: float = 30.0):
+        if scaling not in self.SCALINGS:
+            raise ValueError("scaling is jacobi or none")
+        self.handle, self.A = handle, A
+        self.degree, self.scaling, self.dtype = int(degree), scaling, A.dtype
+        self._c = C.c_void_p()
+        pos = C.c_int(-1)
+        st = rsp.rsp_cheby_create(handle.ptr, A._mat, self.degree, self.SCALINGS[scaling], float(ratio),
+                                  C.byref(pos), C.byref(self._c))
+        if st != _lib.STATUS_SUCCESS:
+            err = RspError(st, "rsp_cheby_create")
+            err.position = pos.value
+            raise err
+
+    @property
+    def bounds(self) -> tuple[float, float]:
+        """(lmin, lmax) the coefficients are computed from."""
+        lo, hi = C.c_double(), C.c_double()
+        check(rsp.rsp_cheby_get_bounds(self._c, C.byref(lo), C.byref(hi)), "rsp_cheby_get_bounds")
+        return lo.value, hi.value
+
+    def set_bounds(self, lmin: float, lmax: float) -> None:
+        check(rsp.rsp_cheby_set_bounds(self._c, float(lmin), float(lmax)), "rsp_cheby_set_bounds")
+
+    def apply(self, r: torch.Tensor, z: torch.Tensor | None = None) -> torch.Tensor:
+        """z = M^-1 r on the handle's stream; r is unchanged and may not be z."""
+        if r.dtype != self.dtype or r.numel() != self.A.m:
+            raise ValueError("r has the wrong dtype or length")
+        if z is None:
+            z = torch.empty_like(r)
+        elif z.dtype != self.dtype or z.numel() != self.A.m:
+            raise ValueError("z has the wrong dtype or length")
+        check(rsp.rsp_cheby_apply(self.handle.ptr, self._c, C.c_void_p(r.data_ptr()), C.c_void_p(z.data_ptr())),
+              "rsp_cheby_apply")
+        return z
+
+    def close(self) -> None:
+        if self._c:
+            rsp.rsp_cheby_destroy(self._c)
+            self._c = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cheby_coefficients(degree: int, lmin: float, lmax: float):
+    """(c0, a, b) of the polynomial in fp64, before the rounding to its type:
+    a[j - 1], b[j - 1] belong to term j = 1 .. degree - 1
+    (rsp_cheby_coefficients_host; no device needed)."""
+    c0 = C.c_double()
+    a, b = np.zeros(max(int(degree) - 1, 1)), np.zeros(max(int(degree) - 1, 1))
+    dp = C.POINTER(C.c_double)
+    check(rsp.rsp_cheby_coefficients_host(int(degree), float(lmin), float(lmax), C.byref(c0),
+                                          a.ctypes.data_as(dp), b.ctypes.data_as(dp)),
+          "rsp_cheby_coefficients_host")
+    return c0.value, a[:int(degree) - 1], b[:int(degree) - 1]
+
+
+def _precond_args(ilu, factor, cheby):
+    """The checks the solvers share on ilu= / factor= / cheby=."""
+    if cheby is not None and (ilu is not None or factor is not None):
+        raise ValueError("cheby= and ilu= / factor= exclude each other")
+    if ilu is not None and factor is None:
+        raise ValueError("an ILU(0) preconditioner needs its factored values")
+
+
 class SolveResult:
     """What BiCGStab.solve, CG.solve and GMRES.solve return: x (the solution tensor), iters, relres
     (recurrence ||r|| / ||b|| at the last check), reason (_lib.SOLVE_*) and
@@ -449,19 +533,24 @@ class BiCGStab:
     """Right-preconditioned BiCGStab on A (rsp_bicgstab_*), M = L U from the
     ILU(0) `factor` values of `ilu` (analysed, factored by the caller), or
     M = I without `ilu`. A's dtype is the iteration type; factor's dtype (the
-    preconditioner type) must not be wider. A, ilu and factor are kept alive."""
+    preconditioner type) must not be wider. A, ilu and factor are kept alive.
+    cheby= (a Cheby on A, or on a float32 SpMat of the same pattern) uses that
+    polynomial as M^-1 instead; it excludes ilu= and factor=."""
 
     CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
 
     def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
-                 factor: torch.Tensor | None = None):
-        if ilu is not None and factor is None:
-            raise ValueError("an ILU(0) preconditioner needs its factored values")
+                 factor: torch.Tensor | None = None, cheby: Cheby | None = None):
+        _precond_args(ilu, factor, cheby)
         if factor is not None and factor.dtype not in _DT:
             raise TypeError("factor must be float64 or float32")
-        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.handle, self.A, self.ilu, self.factor, self.cheby = handle, A, ilu, factor, cheby
         self.dtype = A.dtype
         self._s = C.c_void_p()
+        if cheby is not None:
+            check(rsp.rsp_bicgstab_create_cheby(handle.ptr, A._mat, cheby._c, C.byref(self._s)),
+                  "rsp_bicgstab_create_cheby")
+            return
         check(rsp.rsp_bicgstab_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
                                       _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
                                       _ptr(factor) if ilu is not None else None, C.byref(self._s)),
@@ -507,14 +596,17 @@ class CG:
     CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
 
     def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
-                 factor: torch.Tensor | None = None):
-        if ilu is not None and factor is None:
-            raise ValueError("an ILU(0) preconditioner needs its factored values")
+                 factor: torch.Tensor | None = None, cheby: Cheby | None = None):
+        _precond_args(ilu, factor, cheby)
         if factor is not None and factor.dtype not in _DT:
             raise TypeError("factor must be float64 or float32")
-        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.handle, self.A, self.ilu, self.factor, self.cheby = handle, A, ilu, factor, cheby
         self.dtype = A.dtype
         self._s = C.c_void_p()
+        if cheby is not None:
+            check(rsp.rsp_cg_create_cheby(handle.ptr, A._mat, cheby._c, C.byref(self._s)),
+                  "rsp_cg_create_cheby")
+            return
         check(rsp.rsp_cg_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
                                 _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
                                 _ptr(factor) if ilu is not None else None, C.byref(self._s)),
@@ -559,15 +651,18 @@ class GMRES:
     CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
 
     def __init__(self, handle: Handle, A: SpMat, ilu: Ilu0 | None = None,
-                 factor: torch.Tensor | None = None, restart: int = 30):
-        if ilu is not None and factor is None:
-            raise ValueError("an ILU(0) preconditioner needs its factored values")
+                 factor: torch.Tensor | None = None, restart: int = 30, cheby: Cheby | None = None):
+        _precond_args(ilu, factor, cheby)
         if factor is not None and factor.dtype not in _DT:
             raise TypeError("factor must be float64 or float32")
-        self.handle, self.A, self.ilu, self.factor = handle, A, ilu, factor
+        self.handle, self.A, self.ilu, self.factor, self.cheby = handle, A, ilu, factor, cheby
         self.dtype = A.dtype
         self.restart = int(restart)
         self._s = C.c_void_p()
+        if cheby is not None:
+            check(rsp.rsp_gmres_create_cheby(handle.ptr, A._mat, cheby._c, self.restart, C.byref(self._s)),
+                  "rsp_gmres_create_cheby")
+            return
         check(rsp.rsp_gmres_create(handle.ptr, A._mat, ilu._info if ilu is not None else None,
                                    _DT[factor.dtype] if ilu is not None else _DT[A.dtype],
                                    _ptr(factor) if ilu is not None else None, self.restart,
@@ -612,23 +707,29 @@ class Refine:
     ("bicgstab", "cg" or "gmres" with `restart`). A is the fp64 matrix, A_low an
     fp32 SpMat over the same pattern (values narrowed, e.g. by convert_scaled);
     `ilu` (analysed) with its fp32 `factor_low` is the inner preconditioner, or
-    M = I without. A, A_low, ilu and factor_low are kept alive."""
+    M = I without; cheby= (a Cheby built on A_low) uses that polynomial instead.
+    A, A_low, ilu and factor_low are kept alive."""
 
     CONVERGED, MAX_ITERS, BREAKDOWN = _lib.SOLVE_CONVERGED, _lib.SOLVE_MAX_ITERS, _lib.SOLVE_BREAKDOWN
     STAGNATED = _lib.SOLVE_STAGNATED
     METHODS = {"bicgstab": _lib.REFINE_BICGSTAB, "cg": _lib.REFINE_CG, "gmres": _lib.REFINE_GMRES}
 
     def __init__(self, handle: Handle, A: SpMat, A_low: SpMat, ilu: Ilu0 | None = None,
-                 factor_low: torch.Tensor | None = None, method: str = "gmres", restart: int = 30):
+                 factor_low: torch.Tensor | None = None, method: str = "gmres", restart: int = 30,
+                 cheby: Cheby | None = None):
         if method not in self.METHODS:
             raise ValueError("method is bicgstab, cg or gmres")
-        if ilu is not None and factor_low is None:
-            raise ValueError("an ILU(0) preconditioner needs its factored values")
+        _precond_args(ilu, factor_low, cheby)
         if factor_low is not None and factor_low.dtype != torch.float32:
             raise TypeError("factor_low must be float32")
         self.handle, self.A, self.A_low, self.ilu, self.factor_low = handle, A, A_low, ilu, factor_low
+        self.cheby = cheby
         self.method, self.restart = method, int(restart)
         self._s = C.c_void_p()
+        if cheby is not None:
+            check(rsp.rsp_refine_create_cheby(handle.ptr, A._mat, A_low._mat, cheby._c, self.METHODS[method],
+                                              self.restart, C.byref(self._s)), "rsp_refine_create_cheby")
+            return
         check(rsp.rsp_refine_create(handle.ptr, A._mat, A_low._mat, ilu._info if ilu is not None else None,
                                     _ptr(factor_low) if ilu is not None else None, self.METHODS[method],
                                     self.restart, C.byref(self._s)), "rsp_refine_create")
@@ -777,6 +878,7 @@ def csr_transpose_host(rowptr, colidx, n_cols: int):
     return t_rp, t_ci, perm
 
 
-__all__ = ["Handle", "SpMat", "Ilu0", "BiCGStab", "CG", "GMRES", "Refine", "SolveResult", "dot", "orthogonalize",
+__all__ = ["Handle", "SpMat", "Ilu0", "Cheby", "cheby_coefficients", "BiCGStab", "CG", "GMRES", "Refine",
+           "SolveResult", "dot", "orthogonalize",
            "convert_scaled", "refine_update", "upload_csr", "gather", "scatter", "csr2csc", "csr_transpose_host",
            "RspError"]

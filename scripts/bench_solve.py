@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""ILU(0)-preconditioned BiCGStab, GMRES(m) or CG on the moderate surrogates: does
-a narrower preconditioner reach the same residual in less time?
+"""ILU(0)- or Chebyshev-preconditioned BiCGStab, GMRES(m) or CG on the moderate
+surrogates: does a narrower preconditioner, or one made of SpMVs alone, reach the
+same residual in less time?
 
     python scripts/bench_solve.py [--names A,B] [--scale S] [--rtol R] [--maxit N]
                                   [--method bicgstab|gmres|cg] [--restart M]
                                   [--both-triangles] [--out FILE.jsonl]
                                   [--refine] [--inner-rtol R]
+                                  [--cheby K[,K..]] [--cheby-ratio R]
 
 Per matrix (b = 1, x0 = 0, fp64 iteration) and per configuration
     fp64      fp64 ILU(0) factor and solves
@@ -38,6 +40,16 @@ way is not guaranteed positive definite: BREAKDOWN is then the result.
 --both-triangles gives BiCGStab and GMRES the same expanded matrices (and the
 same skipping), for a comparison on equal systems.
 
+--cheby K[,K..]: after the ILU(0) configurations (all of them, or those of
+--configs; "--configs none" leaves the polynomial ones alone), two more per
+degree K: chebyK (an fp64 Chebyshev polynomial preconditioner, rsp_cheby_*,
+Jacobi scaling, on [lmax / R, lmax] with lmax the Gershgorin bound and R =
+--cheby-ratio, default 30) and chebyK-fp32 (the polynomial on the fp32 values,
+under the fp64 iteration). The record has the same fields; apply_ms is one
+polynomial apply (K - 1 SpMVs and K kernels), setup_ms the host-blocking
+rsp_cheby_create (wall clock), and ms_per_iter = solve_ms / iterations is added
+to every record, ILU ones included.
+
 --refine: instead of the three configurations, one line per matrix for
 mixed-precision iterative refinement (rsp_refine_*: fp64 residuals and updates
 around all-fp32 solves by --method to --inner-rtol, default 1e-4, each of at
@@ -55,6 +67,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,7 +76,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from respasol_amd import _lib, csr  # noqa: E402
-from respasol_amd.sparse import (CG, GMRES, BiCGStab, Handle, Ilu0, Refine, RspError, SpMat,  # noqa: E402
+from respasol_amd.sparse import (CG, GMRES, BiCGStab, Cheby, Handle, Ilu0, Refine, RspError, SpMat,  # noqa: E402
                                  convert_scaled, upload_csr)
 
 CONFIGS = (("fp64", torch.float64, False), ("fp32", torch.float32, False), ("fp32ftz", torch.float32, True))
@@ -147,11 +160,65 @@ def run_one(name, A, cfg, rtol, maxit, method="bicgstab", restart=30):
         rec["apply_ms"] = timed_ms(lambda: [apply() for _ in range(calls)]) / calls
         rec["own_ms"] = rec["solve_ms"] - res.iters * per_iter * (rec["spmv_ms"] + rec["apply_ms"])
         rec["own_share"] = rec["own_ms"] / rec["solve_ms"] if rec["solve_ms"] > 0 else 0.0
+        rec["ms_per_iter"] = rec["solve_ms"] / max(res.iters, 1)
         return rec
     finally:
         if solver is not None:
             solver.close()
         ilu.close()
+        mat.close()
+        h.close()
+
+
+def run_cheby(name, A, degree, pdt, rtol, maxit, method="bicgstab", restart=30, ratio=30.0):
+    """As run_one, with the degree-`degree` Chebyshev polynomial of type pdt as M^-1."""
+    label = f"cheby{degree}" + ("-fp32" if pdt == torch.float32 else "")
+    rec = {"matrix": name, "config": label, "method": method, "n": A.m, "nnz": A.nnz_stored, "degree": degree,
+           "ratio": ratio}
+    per_iter = 2 if method == "bicgstab" else 1
+    h = Handle()
+    rp, ci, va = upload_csr(A.rowptr, A.colidx, A.values)
+    mat = SpMat(h, rp, ci, va, A.n)
+    low = SpMat(h, rp, ci, convert_scaled(h, va, exp2=0, dtype=torch.float32), A.n) if pdt == torch.float32 else None
+    poly = solver = None
+    try:
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            poly = Cheby(h, low if low is not None else mat, degree, "jacobi", ratio)
+            rec["setup_ms"] = (time.perf_counter() - t0) * 1e3
+            rec["lmin"], rec["lmax"] = poly.bounds
+            solver = (GMRES(h, mat, restart=restart, cheby=poly) if method == "gmres"
+                      else CG(h, mat, cheby=poly) if method == "cg" else BiCGStab(h, mat, cheby=poly))
+        except RspError as e:
+            rec["error"] = str(e)
+            return rec
+        b = torch.ones(A.m, dtype=torch.float64, device="cuda")
+        res = solver.solve(b, rtol=rtol, max_iters=maxit)  # warm-up
+        rec.update(iters=res.iters, applies=per_iter * res.iters, reason=res.reason, relres=res.relres,
+                   true_relres=true_relres(A, res.x.cpu().numpy()))
+        rec["solve_ms"] = timed_ms(lambda: solver.solve(b, rtol=rtol, max_iters=maxit))
+        calls = 2 * max(res.iters, 1)
+        x = torch.ones(A.m, dtype=torch.float64, device="cuda")
+        y = torch.empty_like(x)
+        spmv = mat.bind(x, y)
+        spmv()
+        rec["spmv_ms"] = timed_ms(lambda: [spmv() for _ in range(calls)]) / calls
+        px = torch.ones(A.m, dtype=pdt, device="cuda")
+        pz = torch.empty_like(px)
+        poly.apply(px, pz)
+        rec["apply_ms"] = timed_ms(lambda: [poly.apply(px, pz) for _ in range(calls)]) / calls
+        rec["own_ms"] = rec["solve_ms"] - res.iters * per_iter * (rec["spmv_ms"] + rec["apply_ms"])
+        rec["own_share"] = rec["own_ms"] / rec["solve_ms"] if rec["solve_ms"] > 0 else 0.0
+        rec["ms_per_iter"] = rec["solve_ms"] / max(res.iters, 1)
+        return rec
+    finally:
+        if solver is not None:
+            solver.close()
+        if poly is not None:
+            poly.close()
+        if low is not None:
+            low.close()
         mat.close()
         h.close()
 
@@ -215,6 +282,8 @@ def main(argv=None):
     ap.add_argument("--refine", action="store_true",
                     help="mixed-precision iterative refinement beside the fp64 iteration under the fp32 factor")
     ap.add_argument("--inner-rtol", type=float, default=1e-4, help="--refine: the inner solves' rtol")
+    ap.add_argument("--cheby", default="", help="comma-separated degrees of Chebyshev polynomial configurations")
+    ap.add_argument("--cheby-ratio", type=float, default=30.0, help="--cheby: lmin = lmax / this")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_solve.py needs an MI355X: there is no CPU fallback")
@@ -242,6 +311,14 @@ def main(argv=None):
             if out:
                 out.write(line + "\n")
                 out.flush()
+        for degree in [int(k) for k in args.cheby.split(",") if k]:
+            for pdt in (torch.float64, torch.float32):
+                line = json.dumps(run_cheby(name, A, degree, pdt, args.rtol, args.maxit, args.method, args.restart,
+                                            args.cheby_ratio))
+                print(line, flush=True)
+                if out:
+                    out.write(line + "\n")
+                    out.flush()
     if out:
         out.close()
 
